@@ -9,6 +9,12 @@
 Prints ONE JSON line on rank 0.  `value` = clip positions (10,300 per clip) per second over all GPUs,
 inputs resident in HBM.  A "step" = one optimiser step over `--clips-per-gpu` clips (default 256: the
 global batch of 2048 of BASELINE.json at 8 GPUs), micro-batched with gradient accumulation.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = one timed step).
+`--full` adds the measurements that take runs of their own after the timed region: the per-kernel leg
+(`roofline`, `hbm_paths`, `kernel_breakdown`), BASELINE configs 4 and 5 (`extra`), the CPU oracle
+(`cpu_baseline`) and, with a gradient reducer, one instrumented exchange step (`exchange_ms`, ...).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -217,6 +223,29 @@ def extra_config5(device, clips=64, mb=32, steps=2):
     return out
 
 
+def dump_outputs(path, losses, gnorm, eng, per_tensor=8192):
+    """`--dump-outputs`: what the last timed step handed its caller - `loss.npy` (the step's mean loss, then the per-modality
+    losses in the model's modality order) and `grad_norm.npy` (the global gradient norm before clipping) - and
+    `params_sample.npy`: the fp32 master weights that step's AdamW update left, at up to `per_tensor` seeded positions of
+    every parameter (reference state-dict keys in sorted order, positions drawn from a crc32 of the key; ego-b: ~6 MB).
+    All float32; the inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), losses.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "grad_norm.npy"), gnorm.detach().float().reshape(-1).cpu().numpy())
+    parts = []
+    for key, v in sorted(eng.state_dict().items()):
+        if key.endswith("pos_emb") or (key.endswith(".bias") and "norm" in key):     # buffers, not parameters
+            continue
+        flat = v.reshape(-1)
+        idx = np.random.default_rng(zlib.crc32(key.encode())).integers(0, flat.numel(), size=min(flat.numel(), per_tensor))
+        parts.append(flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+    sample = np.concatenate(parts)
+    assert sample.nbytes <= 48 << 20, sample.nbytes                  # the three files stay under 64 MB
+    np.save(os.path.join(path, "params_sample.npy"), sample)
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: this process (which has not touched the
     GPU and never will) starts the N ranks as ONE child `python -m torch.distributed.run` (one rank per GPU, RCCL), lets
@@ -261,12 +290,17 @@ def self_launch(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel leg, the config-4 / config-5 extras, the CPU baseline and "
+                         "(with a gradient reducer) one instrumented exchange step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0)")
     ap.add_argument("--model", default="egom2p_base_12e_12d_swiglu_nobias")
     ap.add_argument("--clips-per-gpu", type=int, default=256)
     ap.add_argument("--micro-batch", type=int, default=64,
-                    help="clips per forward/backward (accumulated to --clips-per-gpu); 64 measured best on MI355X: 32 -1.5 %, 128 -0.6 %")
+                    help="clips per forward/backward (accumulated to --clips-per-gpu); 64 measured best on MI355X: 32 -1.5 %%, 128 -0.6 %%")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=["survey-fp32", "quick", "full", "full-fp32", "full-bf16"], default="survey-fp32",
                     help="survey-fp32 (default): SURVEY 8(d)'s fp32 legs - warm-up + median of 5 at B = 1 and B = 4 - within a budget of "
@@ -287,6 +321,8 @@ def main():
                          "ego-b_mod4_500b_clariden_2048_camcv_depthdenoise.yaml), where the exchange is NOT hidden by the backward")
     ap.add_argument("--no-extras", action="store_true", help="skip the config-4 / config-5 measurements appended after the timed region (N = 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.preset == "yaml4":
         args.clips_per_gpu, args.micro_batch = 4, 4
     under_launcher = "WORLD_SIZE" in os.environ and ("TORCHELASTIC_RUN_ID" in os.environ or int(os.environ["WORLD_SIZE"]) > 1)
@@ -371,10 +407,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(losses[0].item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses, gnorm, eng)
 
     # the timed steps above ran the exchange exactly as TrainStep runs it (no per-bucket event pairs, no extra
     # waits); exchange_ms / exposed_ms / overlap_frac come from ONE more, instrumented step outside the timed region
-    if step.reducer is not None:
+    if args.full and step.reducer is not None:
         step.reducer.timing = True
         run_step(args.warmup + args.steps)
         torch.cuda.synchronize()
@@ -405,7 +443,7 @@ def main():
     }
     out.update(dp_extra)
 
-    if rank == 0 and not args.no_kernel_profile:
+    if args.full and rank == 0 and not args.no_kernel_profile:
         # live HIP-event timing of one micro-batch forward+backward, per kernel class
         kt = KernelTimer()
         pair, eng.pair_stream = eng.pair_stream, None      # per-kernel times: every launch alone (the timed steps above pair wgrad GEMMs with LayerNorm backward launches)
@@ -472,9 +510,11 @@ def main():
         out["kernel_breakdown"] = {k: {"ms": round(v["ms"], 3), "calls": v["calls"], "tflops": round(v["tflops"], 1),
                                         "gbs": round(v["gbs"], 1)} for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"])}
     sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    cpu_leg = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if cpu_leg:
         sd_cpu = {k: v.detach().float().cpu().clone() for k, v in eng.state_dict().items()}
-    if rank == 0 and world == 1 and not args.no_extras and args.model == "egom2p_base_12e_12d_swiglu_nobias" and not args.fp8:
+    if (args.full and rank == 0 and world == 1 and not args.no_extras and args.model == "egom2p_base_12e_12d_swiglu_nobias"
+            and not args.fp8):
         # Driver-witnessed numbers for BASELINE configs 4 and 5 (the headline fields above stay config 2): measured AFTER the
         # timed region, in this process, on fresh models - the ego-b training engine's 110 GB are released first
         del step, mbs
@@ -488,7 +528,7 @@ def main():
             except Exception as e:                                   # an extra must never cost the headline line
                 out["extra"][key] = {"error": f"{type(e).__name__}: {e}"}
         eng = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu_leg:
         out["cpu_baseline"] = cpu_baseline(cfg, sd_cpu, synth, budgets, rank, [m.name for m in cfg.mods], n_enc, n_dec, args.cpu_baseline)
     if dist.is_initialized():
         dist.barrier()

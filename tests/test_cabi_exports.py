@@ -84,6 +84,31 @@ def test_bench_counts_the_flops_the_survey_states():
     assert abs(3.0 * f / 10300 / 406.9e6 - 1.0) < 1e-3
 
 
+def test_bench_dump_outputs_are_float32_and_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: the step's losses, gradient norm and a weight sample at positions fixed by the keys -
+    float32 .npy files that two dumps of the same state write bit for bit, and the sample holds the weights' own values."""
+    import importlib.util
+    import numpy as np
+    import torch
+    from egom2p_amd import synth
+    from egom2p_amd.config import MODEL_CFGS
+    spec = importlib.util.spec_from_file_location("bench_mod_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    sd = synth.build_state_dict(MODEL_CFGS["ego_tiny_2e_2d"], seed=1)
+    eng = type("FakeEngine", (), {"state_dict": lambda self: sd})()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor([3.0, 1.0, 2.0]), torch.tensor([0.5]), eng, per_tensor=64)
+    for f in ("loss.npy", "grad_norm.npy", "params_sample.npy"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    params = {k: v for k, v in sd.items() if not k.endswith("pos_emb") and not (k.endswith(".bias") and "norm" in k)}
+    sample = np.load(tmp_path / "a" / "params_sample.npy")
+    assert sample.size == sum(min(v.numel(), 64) for v in params.values())
+    pool = np.concatenate([v.float().reshape(-1).numpy() for v in params.values()])
+    assert np.isin(sample, pool).all()
+
+
 def test_head_storage_layouts():
     """Host logic of the padded storage (engine.head_layout): heads of 64 unchanged (even counts only); other head dimensions
     padded to 96 / 128 with as many all-zero phantom heads as make the row width a multiple of 128 - the narrowest rows win."""
