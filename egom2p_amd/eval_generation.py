@@ -1,10 +1,12 @@
 """The reference's four generation scripts on MI355X - `eval_model_rgb2depth.py` (:46-96), `eval_model_rgb2cam.py` (:40-95),
 `eval_model_rgb2gaze.py` (:41-96), `eval_model_depth2rgb.py` (:34-91): one conditioning modality, one target modality, ROAR
 with a linear token schedule, temperature 0.01, CFG 2.0 over the growing conditioning, top-p 0.8, one clip batch per call -
-on the HIP engine.  The Cosmos video tokenizer (external TorchScript blobs) and the decoding / plotting of the predicted
-tokens are outside the hot-path scope: the conditioning clip is given as Cosmos token ids (an .npz with a (5,32,32) int
-array, e.g. the reference's example_data/rgb2cam_egoexo.npz), or synthetic ids, and the predicted token ids are written to
-an .npz.  The root-level `eval_model_<task>.py` scripts call `main(<task>)`.
+on the HIP engine.  `--scheme maskgit` runs the same task with the reference's other parallel-decoding scheme
+(`--token-schedule cosine --temp-schedule linear`, say); the defaults are the reference scripts' ROAR run.  The Cosmos video
+tokenizer (external TorchScript blobs) and the decoding / plotting of the predicted tokens are outside the hot-path scope:
+the conditioning clip is given as Cosmos token ids (an .npz with a (5,32,32) int array, e.g. the reference's
+example_data/rgb2cam_egoexo.npz), or synthetic ids, and the predicted token ids are written to an .npz.  The root-level
+`eval_model_<task>.py` scripts call `main(<task>)`.
 """
 from __future__ import annotations
 
@@ -31,7 +33,7 @@ TASKS = {
 
 def main(task: str = "rgb2depth"):
     t = TASKS[task]
-    ap = argparse.ArgumentParser(description=f"{task} generation (ROAR {t['steps']} steps, CFG 2.0, top-p 0.8)")
+    ap = argparse.ArgumentParser(description=f"{task} generation (ROAR or MaskGIT, {t['steps']} steps, CFG 2.0, top-p 0.8)")
     ap.add_argument("--model", default="egom2p_base_12e_12d_swiglu_nobias")
     ap.add_argument("--ckpt", default="", help="reference-format checkpoint ({'model': state_dict}); random init if empty")
     ap.add_argument("--tokens", default="", help=".npz with (5,32,32) Cosmos ids of the conditioning clip; synthetic if empty")
@@ -41,7 +43,13 @@ def main(task: str = "rgb2depth"):
     ap.add_argument("--no-graphs", action="store_true", help="launch kernels one by one instead of replaying hipGraphs")
     ap.add_argument("--graph", choices=["schedule", "pass"], default="schedule",
                     help="schedule: all passes + samplers + scatters of a clip batch are ONE captured graph; pass: one graph per pass")
+    ap.add_argument("--scheme", choices=["roar", "maskgit"], default="roar", help="parallel-decoding scheme (generate.py:1058-1079)")
+    ap.add_argument("--token-schedule", choices=["linear", "cosine"], default="linear",
+                    help="tokens per step of --scheme maskgit (ROAR is always linear, generate.py:272-275)")
+    ap.add_argument("--temp-schedule", default="constant", help="constant, linear or onex:{min_t}:{power} (generate.py:280-289)")
     args = ap.parse_args()
+    if args.scheme == "roar":
+        args.token_schedule = "linear"
     torch.set_grad_enabled(False)
     device = "cuda"
     mods = ["tok_rgb", "tok_depth", "tok_cam", "tok_gaze"]
@@ -57,8 +65,8 @@ def main(task: str = "rgb2depth"):
     cond_domains, target_domains, tokens_per_target = [t["cond"]], [t["target"]], [t["tokens"]]
     schedule = build_chained_generation_schedules(
         cond_domains=cond_domains, target_domains=target_domains, tokens_per_target=tokens_per_target,
-        autoregression_schemes=["roar"], decoding_steps=[t["steps"]], token_decoding_schedules=["linear"], temps=[0.01],
-        temp_schedules=["constant"], cfg_scales=[2.0], cfg_schedules=["constant"], cfg_grow_conditioning=True)
+        autoregression_schemes=[args.scheme], decoding_steps=[t["steps"]], token_decoding_schedules=[args.token_schedule],
+        temps=[0.01], temp_schedules=[args.temp_schedule], cfg_scales=[2.0], cfg_schedules=["constant"], cfg_grow_conditioning=True)
     top_p, top_k = 0.8, 0.0
 
     def generate(sample):
@@ -87,8 +95,10 @@ def main(task: str = "rgb2depth"):
             generate(sample)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.bench
-        passes = 2 * t["steps"]                                 # conditional + unconditional encoder/decoder pass per step
-        print(json.dumps({"metric": f"{task} generation (ROAR {t['steps']} steps, CFG 2.0, top-p 0.8)", "model": args.model,
+        passes = 2 * len(schedule)                                # conditional + unconditional encoder/decoder pass per step
+        print(json.dumps({"metric": f"{task} generation ({'ROAR' if args.scheme == 'roar' else 'MaskGIT'} {len(schedule)} steps, CFG 2.0, top-p 0.8)",
+                          "model": args.model, "scheme": args.scheme, "token_schedule": args.token_schedule,
+                          "temp_schedule": args.temp_schedule,
                           "graph": "none" if args.no_graphs else args.graph, "batch": args.batch, "s_per_clip": dt / args.batch,
                           "clips_per_s": args.batch / dt, "passes_per_clip": passes, "ms_per_pass": dt / passes * 1e3}))
     print(f"done: {t['target']} tokens", tuple(out[t["target"]]["tensor"].shape))

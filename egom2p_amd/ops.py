@@ -416,6 +416,37 @@ def sample_cfg_topp(cond, uncond, V, cfg_scale, top_p, temperature, uniforms, ou
                                        _p(out_prob), rows, _stream()), "ego_sample_cfg_topp")
 
 
+def maskgit_positions(target_mask, M: int, out_pos=None):
+    """[B, M] int64: per batch row the first M indices of argsort(target_mask + arange(T) * 1e-6) - open positions ascending,
+    then closed ones ascending (forward_mask_decoder_maskgit, egom2p/models/generate.py:463-467)"""
+    _need_cuda(target_mask)
+    B, T = target_mask.shape
+    if target_mask.dtype != torch.bool or not target_mask.is_contiguous():
+        raise L.EgoHipError("maskgit_positions: target_mask must be a contiguous bool [B, T] tensor")
+    if out_pos is None:
+        out_pos = torch.empty(B, int(M), device=target_mask.device, dtype=torch.int64)
+    check(L.load().ego_maskgit_positions(_p(target_mask), B, T, int(M), _p(out_pos), _stream()), "ego_maskgit_positions")
+    return out_pos
+
+
+def maskgit_select(tokens, probs, positions, num_select: int, tensor, input_mask, target_mask, out_idx=None):
+    """Commit the min(num_select, M) decoder rows of largest probability IN PLACE: tensor[b, pos] = token, input_mask[b, pos] =
+    False, target_mask[b, pos] = True (select_tokens_batched + the scatters of maskgit_step_batched, generate.py:393-402, 660-663).
+    tokens int32 / probs float32 / positions int64 [B, M]; tensor int64, masks bool [B, T]; out_idx (optional) int64 [B, K]:
+    the chosen rows, ascending.  Ties: strictly larger first, then equal ones in ascending row order."""
+    _need_cuda(tokens, probs, positions, tensor, input_mask, target_mask, out_idx)
+    B, M = positions.shape
+    T = tensor.shape[1]
+    for t, dt, shape in ((tokens, torch.int32, (B, M)), (probs, torch.float32, (B, M)), (positions, torch.int64, (B, M)),
+                         (tensor, torch.int64, (B, T)), (input_mask, torch.bool, (B, T)), (target_mask, torch.bool, (B, T))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise L.EgoHipError(f"maskgit_select: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    if out_idx is not None and (out_idx.dtype != torch.int64 or tuple(out_idx.shape) != (B, min(int(num_select), M)) or not out_idx.is_contiguous()):
+        raise L.EgoHipError("maskgit_select: out_idx must be a contiguous int64 [B, min(num_select, M)] tensor")
+    check(L.load().ego_maskgit_select(_p(tokens), _p(probs), _p(positions), B, M, T, int(num_select), _p(tensor), _p(input_mask),
+                                      _p(target_mask), _p(out_idx), _stream()), "ego_maskgit_select")
+
+
 def top_k_count(top_k, V: int) -> int:
     """The k of `top_k_top_p_filtering` (egom2p/models/generate.py:335-342): an int is a count, a float a share of the vocabulary;
     0 / 0.0 = no top-k filter.  k = 0 from a tiny positive share makes torch.topk(..., 0)[0][..., -1] raise in the reference."""

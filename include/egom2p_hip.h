@@ -25,8 +25,9 @@ extern "C" {
  * ego_layernorm_fwd / ego_attn_*_d64 / ego_loss_finalize and removed ego_grad_scale; 3: round 3 gave ego_layernorm_bwd,
  * ego_bias_grad and ego_embed_bwd a scratch buffer for their atomic-free reductions; 4: ego_layernorm_fwd / _bwd take the
  * row pitch `ld` beside the normalised width D; 5: ego_compact_desc grew `seg_bad`, ego_embed_bwd_desc `vocab`, ego_ce_bwd / ego_ce_fwd_bwd / ego_loss_finalize take loss weights; 6 (round 5): register tokens - ego_compact_desc grew `n_reg`,
- * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; loaders must refuse other versions) */
-#define EGO_ABI_VERSION 6
+ * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
+ * ego_maskgit_positions / ego_maskgit_select; loaders must refuse other versions) */
+#define EGO_ABI_VERSION 7
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -354,6 +355,25 @@ int ego_loss_finalize(const float* nll, const int* ranges, int n_mods, float* ou
 int ego_sample_cfg_topp(const void* cond, const void* uncond, long ld, int V, float cfg_scale, float top_p, int top_k,
                         float temperature, const float* uniforms, int* out_tokens, float* out_prob, int rows,
                         hipStream_t stream);
+/* MaskGIT decoder row order (forward_mask_decoder_maskgit, egom2p/models/generate.py:463-467): out_pos[b, :M] = the first M
+ * indices of argsort(target_mask[b] + arange(T) * 1e-6) = the open positions (mask false) ascending, then the closed ones
+ * ascending.  target_mask: bool [B, T] (one byte per element), out_pos: int64 [B, M], 0 <= M <= T (the reference takes M
+ * from sample 0, :460); M == 0 launches nothing.  One workgroup per batch row, a block prefix scan, no sort. */
+int ego_maskgit_positions(const void* target_mask, int B, int T, int M, long* out_pos, hipStream_t stream);
+/* MaskGIT token selection: select_tokens_batched's torch.topk over the sampled tokens' probabilities (:393-402) and the three
+ * scatters of (guided_)maskgit_step_batched (:660-663, :697-703).  Per batch row b, over the M decoder rows (tokens / probs:
+ * the outputs of ego_sample_cfg_topp, [B, M]; positions: ego_maskgit_positions' [B, M]): the K = min(num_select, M) rows of
+ * largest probability are committed - tensor[b, pos] = token, input_mask[b, pos] = false, target_mask[b, pos] = true (int64 /
+ * bool / bool [B, T], updated in place) - and their row indices are written to out_idx (optional, int64 [B, K]) in ascending
+ * row order.  TIE RULE (this engine's: torch.topk leaves the order of equal values unspecified, and at temperature 0 every
+ * probability is 1): every row whose probability is strictly above the K-th largest value is taken, the remainder is filled
+ * from the rows EQUAL to it in ascending decoder-row order.  Probabilities are >= 0 (the K-th largest is found by a binary
+ * search on their bit patterns); M <= 8192 (EGO_ERR_ARG above; the largest modality has 5120 tokens).  No atomics: results
+ * are bitwise reproducible.  K == 0 launches nothing.  positions must lie in [0, T) and be distinct within a batch row
+ * (ego_maskgit_positions' output is): a chosen row whose position is outside [0, T) commits nothing - the bounds check keeps the
+ * stores inside the three tensors - but is still listed in out_idx. */
+int ego_maskgit_select(const int* tokens, const float* probs, const long* positions, int B, int M, int T, int num_select,
+                       long* tensor, void* input_mask, void* target_mask, long* out_idx, hipStream_t stream);
 
 /* ---- parameters / optimiser ------------------------------------------------------------------ */
 
