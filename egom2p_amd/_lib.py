@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EGOM2P_HIP_LIB", os.path.join(_HERE, "libegom2p_hip.so"))   # override: kernel experiments
 MAX_MODS = 8
 
-ABI_VERSION = 7          # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
+ABI_VERSION = 8          # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
 EPI_BF16, EPI_F32, EPI_RESID, EPI_BIAS_RESID = 0, 1, 2, 3
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
@@ -113,6 +113,8 @@ _SIGS = {
     "ego_bias_grad": [vp, i64, i32, vp, vp, i64, vp],
     "ego_grad_sqnorm": [vp, i64, vp, vp, vp],
     "ego_adamw_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, i32, vp],
+    "ego_adamw_gate": [vp, f32, f32, i32, vp, vp],
+    "ego_adamw_step_gated": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, i32, vp, vp],
     "ego_sample_cfg_topp": [vp, vp, i64, i32, f32, f32, i32, f32, vp, vp, vp, i32, vp],
     "ego_maskgit_positions": [vp, i32, i32, i32, vp, vp],
     "ego_maskgit_select": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],

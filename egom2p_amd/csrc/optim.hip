@@ -108,3 +108,100 @@ extern "C" int ego_adamw_step(float* p, float* g, float* m, float* v, long n, fl
     LAUNCH_CHECK();
     return EGO_OK;
 }
+
+// ---- step gate: skip_grad of the reference loop and the opt-in non-finite guard, decided on the device ----------------------
+//
+// Replaces: the `elif skip_grad is not None` branch of NativeScalerWithGradNormCount.__call__ (egom2p/utils/native_scaler.py:34-40:
+// `if norm >= skip_grad: return norm` in front of optimizer.step()).  The reference reads the norm on the host; here the gate
+// kernel leaves the decision in device memory and the gated AdamW pass reads it, so a step costs no host sync.
+namespace {
+
+// gate: EGO_GATE_WORDS int32 - [0] this call is gated, [1] gated calls since the host last folded them into its step counts,
+// [2] gated calls in total.  One thread, plain loads and stores: no atomics, capturable.
+__global__ __launch_bounds__(64) void adamw_gate_kernel(const double* __restrict__ sqnorm, float gscale, float skip_norm,
+                                                        int skip_nonfinite, int* __restrict__ gate) {
+    if (threadIdx.x != 0) return;
+    const float norm = (float)sqrt(*sqnorm) * gscale;              // as adamw_kernel forms it
+    // a NaN norm compares false, as `norm >= skip_grad` does in the reference: only the guard stops it
+    const int gated = ((skip_norm > 0.f && norm >= skip_norm) || (skip_nonfinite && !isfinite(norm))) ? 1 : 0;
+    gate[0] = gated;
+    gate[1] += gated;
+    gate[2] += gated;
+}
+
+// adamw_kernel's twin (same math, vector width, grid, tail).  gate[0] != 0: p, m, v are not written (g is still zeroed when asked).
+// Otherwise the step count is step - gate[1]: the host counts every call, the device knows how many of them were gated.  The two
+// bias corrections are therefore formed here, once per thread in front of the loop (uniform values: no LDS, no barrier).
+__global__ __launch_bounds__(256) void adamw_gated_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, long n, float lr, float wd, float b1, float b2,
+                                                          float eps, int step_arg, float gscale, float max_norm,
+                                                          const double* __restrict__ sqnorm, int zero_grad,
+                                                          const int* __restrict__ gate) {
+    const long n4 = n >> 2;
+    if (gate[0]) {
+        if (!zero_grad) return;
+        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+            *(f32x4*)(g + i * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            for (long i = n4 * 4; i < n; ++i) g[i] = 0.f;
+        return;
+    }
+    int t = step_arg - gate[1];
+    if (t < 1) t = 1;
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)t));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)t));
+    float coef = gscale;
+    if (max_norm > 0.f && sqnorm) {
+        const float total = (float)sqrt(*sqnorm) * gscale;
+        coef *= fminf(1.f, max_norm / (total + 1e-6f));
+    }
+    const float step = lr / bc1, decay = 1.f - lr * wd;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pp = *(f32x4*)(p + i * 4), gg = *(f32x4*)(g + i * 4), mm = *(f32x4*)(m + i * 4), vv = *(f32x4*)(v + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float ge = gg[e] * coef;
+            pp[e] *= decay;
+            mm[e] = b1 * mm[e] + (1.f - b1) * ge;
+            vv[e] = b2 * vv[e] + (1.f - b2) * ge * ge;
+            pp[e] -= step * (mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps));
+        }
+        *(f32x4*)(p + i * 4) = pp; *(f32x4*)(m + i * 4) = mm; *(f32x4*)(v + i * 4) = vv;
+        if (zero_grad) *(f32x4*)(g + i * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (long i = n4 * 4; i < n; ++i) {
+            const float ge = g[i] * coef;
+            float pe = p[i] * decay;
+            const float me = b1 * m[i] + (1.f - b1) * ge, ve = b2 * v[i] + (1.f - b2) * ge * ge;
+            pe -= step * (me / (sqrtf(ve) / bc2_sqrt + eps));
+            p[i] = pe; m[i] = me; v[i] = ve;
+            if (zero_grad) g[i] = 0.f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int ego_adamw_gate(const double* sqnorm, float gscale, float skip_norm, int skip_nonfinite, int* gate,
+                              hipStream_t stream) {
+    if (!sqnorm || !gate || ((uintptr_t)sqnorm) % 8 || ((uintptr_t)gate) % 4) return EGO_ERR_ARG;
+    EGO_LAUNCH(adamw_gate_kernel, dim3(1), dim3(64), 0, stream, sqnorm, gscale, skip_norm, skip_nonfinite, gate);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long n, float lr, float wd, float beta1, float beta2,
+                                    float eps, int step, float gscale, float max_norm, const double* sqnorm, int zero_grad,
+                                    const int* gate, hipStream_t stream) {
+    if (n <= 0) return EGO_OK;
+    if (step < 1 || !gate || ((uintptr_t)gate) % 4 || ((uintptr_t)p) % 16 || ((uintptr_t)g) % 16 || ((uintptr_t)m) % 16 ||
+        ((uintptr_t)v) % 16)
+        return EGO_ERR_ARG;
+    const long n4 = n / 4;
+    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+    EGO_LAUNCH(adamw_gated_kernel, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, stream, p, g, m, v, n, lr, wd, beta1, beta2, eps,
+                       step, gscale, max_norm, sqnorm, zero_grad, gate);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}

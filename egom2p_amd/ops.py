@@ -339,6 +339,25 @@ def adamw_step(p, g, m, v, lr, wd, step, beta1=0.9, beta2=0.95, eps=1e-8, gscale
                                   _p(sqnorm), int(zero_grad), _stream()), "ego_adamw_step")
 
 
+GATE_WORDS = 4          # EGO_GATE_WORDS: [0] this call gated, [1] gated calls since the last fold, [2] gated calls in total
+
+
+def adamw_gate(sqnorm, gate, gscale=1.0, skip_norm=0.0, skip_nonfinite=False):
+    """Decide on the device whether this optimiser call updates anything (native_scaler.py:34-40 without the host read)."""
+    if gate.dtype != torch.int32 or gate.numel() < GATE_WORDS or sqnorm.dtype != torch.float64:
+        raise L.EgoHipError("adamw_gate: gate must hold GATE_WORDS int32, sqnorm one float64")
+    check(L.load().ego_adamw_gate(_p(sqnorm), gscale, skip_norm, int(bool(skip_nonfinite)), _p(gate), _stream()), "ego_adamw_gate")
+
+
+def adamw_step_gated(p, g, m, v, lr, wd, step, gate, beta1=0.9, beta2=0.95, eps=1e-8, gscale=1.0, max_norm=0.0, sqnorm=None,
+                     zero_grad=False):
+    """`adamw_step` behind `adamw_gate`'s decision; `step` counts every call, the device subtracts the gated ones."""
+    if gate.dtype != torch.int32 or gate.numel() < GATE_WORDS:
+        raise L.EgoHipError("adamw_step_gated: gate must hold GATE_WORDS int32")
+    check(L.load().ego_adamw_step_gated(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, wd, beta1, beta2, eps, step, gscale, max_norm,
+                                        _p(sqnorm), int(zero_grad), _p(gate), _stream()), "ego_adamw_step_gated")
+
+
 def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0):
     """`out`: dict of preallocated tensors (ids_keep,pad,mod_mask,slot,local,tok,ks,ke,n_valid,seg,err), n_reg + n_keep entries per
     sample (n_reg: register tokens in front of the kept rows, encoder only)."""

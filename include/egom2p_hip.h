@@ -27,7 +27,7 @@ extern "C" {
  * row pitch `ld` beside the normalised width D; 5: ego_compact_desc grew `seg_bad`, ego_embed_bwd_desc `vocab`, ego_ce_bwd / ego_ce_fwd_bwd / ego_loss_finalize take loss weights; 6 (round 5): register tokens - ego_compact_desc grew `n_reg`,
  * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
  * ego_maskgit_positions / ego_maskgit_select; loaders must refuse other versions) */
-#define EGO_ABI_VERSION 7
+#define EGO_ABI_VERSION 8
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -392,6 +392,20 @@ int ego_bias_grad(const void* g_bf16, long rows, int D, float* db, float* work, 
 int ego_grad_sqnorm(const float* g, long n, double* out, double* work, hipStream_t stream);
 int ego_adamw_step(float* p, float* g, float* m, float* v, long n, float lr, float wd, float beta1, float beta2, float eps,
                    int step, float gscale, float max_norm, const double* sqnorm, int zero_grad, hipStream_t stream);
+/* The step gate: `skip_grad` of the reference loop (egom2p/utils/native_scaler.py:34-40: `if norm >= skip_grad: return norm` in
+ * front of optimizer.step()) and an opt-in guard against non-finite gradients, decided on the device - no host read.
+ * gate: EGO_GATE_WORDS int32 of device memory, zeroed by the caller once: [0] this call is gated, [1] gated calls since the
+ * caller last reset the word (it subtracts them from its own step counts when it does), [2] gated calls in total.
+ * ego_adamw_gate forms norm = (float)sqrt(*sqnorm) * gscale as ego_adamw_step does and gates when skip_norm > 0 && norm >= skip_norm
+ * (a NaN norm compares false, as in the reference) or when skip_nonfinite != 0 && norm is inf or NaN; one tiny launch, no atomics. */
+#define EGO_GATE_WORDS 4
+int ego_adamw_gate(const double* sqnorm, float gscale, float skip_norm, int skip_nonfinite, int* gate, hipStream_t stream);
+/* ego_adamw_step behind the gate (native_scaler.py:34-40, optim_factory.py:226): gate[0] != 0 writes nothing to p, m, v (g is still
+ * zeroed when zero_grad); otherwise the AdamW step number is step - gate[1] (clamped to >= 1) and the bias corrections are formed
+ * on the device.  Same math, grid and traffic as ego_adamw_step. */
+int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long n, float lr, float wd, float beta1, float beta2, float eps,
+                         int step, float gscale, float max_norm, const double* sqnorm, int zero_grad, const int* gate,
+                         hipStream_t stream);
 
 /* ---- data-parallel gradient exchange (RCCL over xGMI) ---------------------------------------- */
 

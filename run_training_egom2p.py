@@ -12,7 +12,8 @@ the reference's `run_training_egom2p.py` (`python -m torch.distributed.run ... r
 
 The data pipeline (webdataset tars, tokenizers) is outside the hot-path scope: `--data synthetic` feeds
 clips in the reference's `mod_dict` contract (masking.py:236-266) from the counter-based generator.
-Unlike the reference, the loop reads the loss from the device only every `--print_freq` steps.
+Unlike the reference, the loop reads the loss from the device only every `--print_freq` steps; `--skip_grad` (reference :104,
+:737) is therefore decided on the device, and `--skip_nonfinite_grad` does the same for an inf / NaN gradient norm.
 """
 from __future__ import annotations
 
@@ -60,6 +61,9 @@ def get_args(argv=None):
     p.add_argument("--opt_eps", default=1e-8, type=float)
     p.add_argument("--opt_betas", default=[0.9, 0.95], type=float, nargs="+")
     p.add_argument("--clip_grad", default=None, type=float)
+    p.add_argument("--skip_grad", default=None, type=float, help="Skip update if gradient norm larger than threshold (default: %(default)s)")
+    p.add_argument("--skip_nonfinite_grad", action="store_true",
+                   help="pass an update by when its gradient norm is inf or NaN (decided on the device; not in the reference)")
     p.add_argument("--weight_decay", default=0.05, type=float)
     p.add_argument("--weight_decay_end", default=None, type=float, help="final weight decay (default: constant)")
     p.add_argument("--blr", default=1e-4, type=float, help="base lr: lr = blr * global_batch / 256")
@@ -174,6 +178,8 @@ def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, 
     else:
         model.module.unfreeze_all()
     t0, seen = time.time(), 0
+    # steps the device-side gate passed by (--skip_grad without --clip_grad, --skip_nonfinite_grad): read where loss.item() syncs anyway
+    gating = (args.skip_grad is not None and args.clip_grad is None) or args.skip_nonfinite_grad
     for step, x in enumerate(loader):
         it = start_steps + step
         update = (step + 1) % args.accum_iter == 0
@@ -188,12 +194,14 @@ def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, 
             if update:
                 loss, mod_loss = model(mod_dict, num_encoder_tokens=args.num_input_tokens,
                                        num_decoder_tokens=args.num_target_tokens, loss_type=args.loss_type)
-                grad_norm = scaler(loss / args.accum_iter, optimizer, clip_grad=args.clip_grad, parameters=model.parameters(), update_grad=True)
+                grad_norm = scaler(loss / args.accum_iter, optimizer, clip_grad=args.clip_grad, skip_grad=args.skip_grad,
+                                   parameters=model.parameters(), update_grad=True)
             else:
                 with model.no_sync():
                     loss, mod_loss = model(mod_dict, num_encoder_tokens=args.num_input_tokens,
                                            num_decoder_tokens=args.num_target_tokens, loss_type=args.loss_type)
-                    grad_norm = scaler(loss / args.accum_iter, optimizer, clip_grad=args.clip_grad, parameters=model.parameters(), update_grad=False)
+                    grad_norm = scaler(loss / args.accum_iter, optimizer, clip_grad=args.clip_grad, skip_grad=args.skip_grad,
+                                       parameters=model.parameters(), update_grad=False)
         seen += args.batch_size
         if step % args.print_freq == 0:
             lv = loss.item()                                     # the only host sync, every print_freq steps
@@ -204,7 +212,8 @@ def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, 
             gn_txt = f"{grad_norm.item():.3f}" if grad_norm is not None else "-"        # accumulation micro-steps have no norm yet
             print(f"Epoch: [{epoch}] step {step} loss {lv:.4f} " + " ".join(f"{m}_loss {v.item():.3f}" for m, v in mod_loss.items()) +
                   f" grad_norm {gn_txt} lr {optimizer.param_groups[0]['lr']:.3e} wd {optimizer.param_groups[0]['weight_decay']:.4f} "
-                  f"clips/s/gpu {seen / max(dt, 1e-9):.1f}", flush=True)
+                  f"clips/s/gpu {seen / max(dt, 1e-9):.1f}" +
+                  (f" gated_steps {optimizer.gated_total()}" if gating else ""), flush=True)
         if args.max_steps > 0 and step + 1 >= args.max_steps:
             break
     torch.cuda.synchronize()
@@ -255,7 +264,7 @@ def main(args):
     args.lr = args.blr * global_batch / 256                      # reference :498-505
     model = DataParallel(model)
     optimizer = create_optimizer(args, model.module)
-    scaler = NativeScalerWithGradNormCount(enabled=False)        # bf16: GradScaler disabled (:518)
+    scaler = NativeScalerWithGradNormCount(enabled=False, skip_nonfinite=args.skip_nonfinite_grad)   # bf16: GradScaler disabled (:518)
     # ---- epochs / warm-up / cool-down / frozen phase from token budgets (reference :433-470); an "epoch" is epoch_size clips
     tok_per_clip = args.num_input_tokens + args.num_target_tokens
     per_loader_step = tok_per_clip * args.batch_size * world
