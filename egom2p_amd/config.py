@@ -57,6 +57,7 @@ class ModelCfg:
     share_embedding: bool = True       # decoder to_logits tied to decoder token_emb
     eps: float = 1e-6
     num_register_tokens: int = 0       # learned [1, R, dim] rows in front of every sample's encoder tokens (egom2p_model.py:170-171, 381-387)
+    decoder_causal_mask: bool = False  # decoder self-attention under triu(1) | modality separation (egom2p_model.py:459-463, 1029-1051)
 
     @property
     def head_dim(self) -> int:
@@ -93,6 +94,9 @@ MODEL_CFGS: Dict[str, ModelCfg] = {
     "ego_b_2e_2d_reg4": ModelCfg("ego_b_2e_2d_reg4", 768, 2, 2, 12, num_register_tokens=4),
     # untied decoder head (`share_embedding=False`, the FM wrapper's setting: egom2p_model.py:856-858) at parity-test depth
     "ego_b_2e_2d_untied": ModelCfg("ego_b_2e_2d_untied", 768, 2, 2, 12, share_embedding=False),
+    # `decoder_causal_mask=True` (the registered egom2p_base_12e_12d_swiglu_nobias_causal, egom2p_model.py:1029-1051) at the tiny
+    # variant's width (dim 384, 6 heads of 64) and parity-test depth: tests/golden/b2_causal.npz, b2_subset.npz
+    "ego_384_2e_2d_causal": ModelCfg("ego_384_2e_2d_causal", 384, 2, 2, 6, decoder_causal_mask=True),
     "ego_L_1152": ModelCfg("ego_L_1152", 1152, 24, 24, 18),
     "ego_L_1152_2e_2d": ModelCfg("ego_L_1152_2e_2d", 1152, 2, 2, 18),       # ego-L width (BASELINE config 5) at parity-test depth
     # the REGISTERED ego-L geometry (egom2p_model.py:1080-1092: dim 1020, 15 heads of 68, F = 2720) at parity-test depth;

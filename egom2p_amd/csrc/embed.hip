@@ -21,6 +21,7 @@ struct CompactArgs {
     int mod_id[EGO_MAX_MODS];
     int n_mods, T, n_keep, is_decoder;
     int n_reg;                // register rows in front of every sample's kept rows (encoder only): outputs are [B, n_reg + n_keep]
+    int causal;               // decoder only: decoder_causal_mask (egom2p_model.py:459-463) - the cumsum rule gives way to triu(1)
     long long* ids_keep;      // [B, n_keep]
     unsigned char* pad;       // [B, n_keep]
     short* mod_mask;          // [B, n_keep]  (-1 on pads)
@@ -177,12 +178,27 @@ __global__ __launch_bounds__(256) void compact_kernel(CompactArgs a) {
 #pragma unroll
                     for (int k = 0; k < EGO_MAX_MODS; ++k) if (k == m) { sa = segstart[k]; sb = segstart[k + 1]; }
                     const int s0 = min(sa, a.n_keep), s1 = min(sb, a.n_keep);
+                    if (a.causal) {
+                        // decoder_causal_mask: triu(1) | (mod_mask differs) (egom2p_model.py:459-463, 476-479; the
+                        // decoder_attention_mask is not read).  The kept rows of a modality are contiguous, so kept row `out`
+                        // of segment [s0, s1) sees exactly the keys [s0, out + 1).  Every pad key has an index >= nv > out:
+                        // no valid row can see one, so the "visible pad key" error does not exist in this mode.  Pad rows
+                        // (consumed by nobody: mod_mask -1, no loss row, visible to no valid row) get the encoder's pad
+                        // treatment, every valid key.  The decoder side has no register rows (n_reg != 0 is refused).
+                        a.ks[o] = unm ? s0 : 0;
+                        a.ke[o] = unm ? min(s1, out + 1) : nv;
+                        // the rows of a group no longer share one interval: a sample with a group of more than one row
+                        // takes the attention kernels' per-row path (the choice made here rather than in the engine, so
+                        // that every caller of the C-ABI that passes `seg` on is covered)
+                        if (unm && a.seg_bad && s1 - s0 > 1) atomicOr(a.seg_bad + b, 1);
+                    } else {
                     a.ks[o] = s0;
                     a.ke[o] = min(s1, cs);
                     if (cs > nv && nv < a.n_keep) atomicOr(a.err, 1);   // a pad key would be visible: not an interval mask
                     // the data contract's marker (masking.py:262-264) makes every target row see exactly its modality's
                     // segment; anything else sends the sample down the attention kernels' per-row path
                     if (unm && a.seg_bad && cs < s1) atomicOr(a.seg_bad + b, 1);
+                    }
                 } else {
                     a.ks[o] = 0;
                     a.ke[o] = a.n_reg + nv;
@@ -678,9 +694,11 @@ extern "C" int ego_rows_scatter(float* table, const int* rows, const int* count,
     return EGO_OK;
 }
 
-extern "C" int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream) {
+static int compact_launch(const ego_compact_desc* d, int B, int causal, hipStream_t stream) {
     if (!d || d->n_mods <= 0 || d->n_mods > EGO_MAX_MODS || B <= 0) return EGO_ERR_ARG;
+    if (causal && !d->is_decoder) return EGO_ERR_ARG;
     CompactArgs a{};
+    a.causal = causal;
     int T = 0;
     for (int m = 0; m < d->n_mods; ++m) {
         a.mask[m] = (const unsigned char*)d->mask[m];
@@ -702,6 +720,10 @@ extern "C" int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream)
     LAUNCH_CHECK();
     return EGO_OK;
 }
+
+extern "C" int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 0, stream); }
+
+extern "C" int ego_compact_causal(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 1, stream); }
 
 extern "C" int ego_embed_fwd(const ego_embed_desc* d, hipStream_t stream) {
     if (!d || d->rows <= 0 || d->D % 4) return EGO_ERR_ARG;

@@ -137,6 +137,7 @@ class Engine:
         self._alloc_workspaces()
         self.weights_dirty = True
         self._have_fwd = False
+        self.fmods = self.mods                          # the modalities of the last forward (a mod_dict may hold a subset)
         self._ce_done, self._ce_grad = set(), None      # modalities whose CE backward ran inside the forward (loss_grad)
         self.max_graphs = 16                  # captured generation passes kept alive at once (LRU)
         self._iw, self._infer_key = None, None
@@ -751,7 +752,11 @@ class Engine:
         attention workgroup sees one interval; EGOM2P_ATTN_GROUPS=0 keeps the per-row launches."""
         if self.HDP != 64 or not self.attn_groups:
             return {}
-        return dict(seg=self.cd["seg"][:self.B], seg_bad=self.cd["seg_bad"][:self.B])
+        # (the compaction packs (start, count) per PRESENT modality slot: [B, len(present), 2] at the front of the buffer.  A causal
+        #  decoder goes through the same launch: ego_compact_causal raises seg_bad for every sample whose groups are not single rows,
+        #  which sends it down the kernels' per-row interval class - forward, dQ and dK / dV)
+        n = len(self.fmods)
+        return dict(seg=self.cd["seg"].view(-1)[:self.B * n * 2].view(self.B, n, 2), seg_bad=self.cd["seg_bad"][:self.B])
 
     def _attn_bwd(self, q_t, q_off, q_rs, kv_t, k_off, v_off, kv_rs, o_t, do_t, lse, dq_t, dkv_t, ks, ke, r_bs, r_rs, B, Nq, Nk,
                   o_lo=None, seg=None, seg_bad=None):
@@ -779,7 +784,15 @@ class Engine:
         if self.weights_dirty:
             self.refresh_weights()
         cfg, D, A, Fp, N, M = self.cfg, self.D, self.A, self.Fp, self.Ne, self.M      # N: encoder rows per sample (registers included)
-        mods = self.mods
+        # the modalities of this micro-batch: the configured ones present in mod_dict, in configuration order (the reference takes
+        # whatever is there, egom2p_model.py:706-714); slots, loss rows and the loss mean run over these
+        unknown = [k for k in mod_dict if k not in {m.name for m in self.mods}]
+        if unknown:
+            raise KeyError(f"not a configured modality: {unknown}")
+        mods = [m for m in self.mods if m.name in mod_dict]
+        if not mods:
+            raise ValueError("mod_dict holds no modality")
+        self.fmods, n_mods = mods, len(mods)
         B = mod_dict[mods[0].name]["input_mask"].shape[0]
         if B > self.Bmax:
             raise L.EgoHipError(f"batch {B} exceeds the engine's workspace batch {self.Bmax}")
@@ -799,7 +812,7 @@ class Engine:
                     [m.max_tokens for m in mods], [m.id for m in mods], self.N, False, ce, B, n_reg=self.R)
         ops.compact([mod_dict[m.name]["target_mask"] for m in dmods], [flat_ids(m) for m in dmods],
                     [mod_dict[m.name]["decoder_attention_mask"] for m in dmods],
-                    [m.max_tokens for m in dmods], [m.id for m in dmods], M, True, cd, B)
+                    [m.max_tokens for m in dmods], [m.id for m in dmods], M, True, cd, B, causal=bool(cfg.decoder_causal_mask))
         x0 = self.enc[0]["x"] if cfg.encoder_depth else self.x_enc_out
         ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
                       [self.pos[m.name] for m in mods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods],
@@ -811,8 +824,8 @@ class Engine:
         cache = self.__dict__.setdefault("_canon_dev", {})
         if ckey not in cache:                        # one small H2D copy per decoder order, ever (never inside a graph capture)
             cache[ckey] = torch.tensor([mods.index(m) for m in dmods], dtype=I32).to(self.dev)
-        self.canon.copy_(cache[ckey])
-        ops.loss_perm(cd["seg"], self.canon, cd["slot"], cd["tok"], B, M, self.n_mods, self.perm, self.tgt_perm,
+        self.canon[:n_mods].copy_(cache[ckey])
+        ops.loss_perm(cd["seg"], self.canon, cd["slot"], cd["tok"], B, M, n_mods, self.perm, self.tgt_perm,
                       self.ranges, self.perm_base)
 
         # ---- encoder (egom2p_model.py:496-499; Block.forward egom2p_utils.py:356-359)
@@ -879,12 +892,12 @@ class Engine:
             ops.gemm_nt(self.yn, l.wb, lg, ub, m.vocab_size, D, L.EPI_BF16, m_range=self.ranges[c], lda=D, ldb=D, ldc=m.vocab_size)
             if loss_grad is not None and ops.ce_fusable(m.vocab_size):
                 ops.ce_fwd_bwd(lg, m.vocab_size, m.vocab_size, self.tgt_perm, self.ranges[c], ub, self.lse_ce, self.nll, self.gscale,
-                               self.n_mods, loss_w=None if lw is None else lw[c:c + 1])
+                               n_mods, loss_w=None if lw is None else lw[c:c + 1])
                 self._ce_done.add(c)
             else:
                 ops.ce_fwd(lg, m.vocab_size, m.vocab_size, self.tgt_perm, self.ranges[c], ub, self.lse_ce, self.nll)
         # a decoder_attention_mask that is not one interval per row (compaction flag) turns the loss into NaN
-        ops.loss_finalize(self.nll, self.ranges, self.n_mods, self.loss_out, err=cd["err"], loss_w=lw, mod_scale=ms)
+        ops.loss_finalize(self.nll, self.ranges, n_mods, self.loss_out, err=cd["err"], loss_w=lw, mod_scale=ms)
         return self.loss_out[0], {m.name: self.loss_out[1 + c] for c, m in enumerate(mods)}
 
     # ------------------------------------------------------------------------------------ backward
@@ -932,7 +945,7 @@ class Engine:
         assert self._have_fwd, "backward() needs a forward()"
         cfg, D, A, N, M, B = self.cfg, self.D, self.A, self.Ne, self.M, self.B       # N: encoder rows per sample (registers included)
         RN, RM = B * N, B * M
-        mods, ce, cd = self.mods, self.ce, self.cd
+        mods, ce, cd = self.fmods, self.ce, self.cd           # the modalities of the forward (absent ones: no kernel writes their gradients)
         if getattr(self, "_ce_done", None):
             # the forward already turned the logits into d logits with the upstream gradient it was promised
             same = (gscale is self._ce_grad) or (not isinstance(gscale, torch.Tensor) and not isinstance(self._ce_grad, torch.Tensor)
@@ -956,11 +969,11 @@ class Engine:
             V = m.vocab_size
             lg = self.logits[V]
             if c not in self._ce_done:
-                ops.ce_bwd(lg, V, V, self.tgt_perm, self.ranges[c], ub, self.lse_ce, self.gscale, self.n_mods,
+                ops.ce_bwd(lg, V, V, self.tgt_perm, self.ranges[c], ub, self.lse_ce, self.gscale, len(mods),
                            loss_w=self.loss_w[c:c + 1] if getattr(self, "_loss_mode", 0) else None)
             ops.gemm_nt(lg, l.wt, self.dyn, ub, D, V, L.EPI_BF16, m_range=self.ranges[c], lda=V, ldb=V, ldc=D)
             self._wgrad(l.g, lg, self.yn, V, D, ub, ldp=V, ldq=D, m_range=self.ranges[c])
-        for m in reversed(mods):
+        for m in reversed(self.mods):                          # (every bucket is handed over, an absent modality's with zeros)
             done(f"dec_table.{m.name}" if cfg.share_embedding else f"to_logits.{m.name}")
         dres, dres_b = self.dres, self._ring_next()
         ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
@@ -1031,11 +1044,12 @@ class Engine:
         # encoder input embeddings: token rows, mod_emb (emb is used twice: x = tok + emb and context += emb)
         ops.embed_bwd([self.g[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
                       [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, dxe, self.dctx,
-                      ce["slot"], ce["tok"], RN, D, touched=getattr(self, "touched", None))
+                      ce["slot"], ce["tok"], RN, D,
+                      touched=None if getattr(self, "touched", None) is None else [self.touched[self.mods.index(m)] for m in mods])
         if self.R:        # d register_tokens = the encoder input gradient of the register rows, summed over the batch (emb is 0 there)
             ops.reg_grad(dxe, B, N, self.R, D, self.g["register_tokens"])
         done("mod_emb")
-        for m in reversed(mods):
+        for m in reversed(self.mods):
             done(f"enc_table.{m.name}")
         self._join_side()
         self._have_fwd = False
@@ -1393,7 +1407,7 @@ class Engine:
                                 "produce a mask this engine cannot express)")
         B, M, D = self.B, self.M, self.D
         out = {}
-        for m in self.mods:
+        for m in self.fmods:                      # (the modalities of the call: forward_logits walks decoder_mod_dict, :544)
             l = self.lin[self.logit_key[m.name]]
             lg = torch.empty(B * M, m.vocab_size, device=self.dev, dtype=BF16)
             ops.gemm_nt(self.yn, l.wb, lg, B * M, m.vocab_size, D, L.EPI_BF16, lda=D, ldb=D, ldc=m.vocab_size)

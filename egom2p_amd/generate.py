@@ -18,6 +18,10 @@ A MaskGIT step decodes ALL open target positions (`ego_maskgit_positions`: open 
 for each with the same sampler kernel - which also returns the sampled token's probability - and commits the `num_tokens`
 rows of largest probability (`ego_maskgit_select`: no sort; ties go to the lower decoder row).  Its only random
 numbers are the sampling uniforms.
+
+A model with `decoder_causal_mask=True` generates exactly like a standard one: the reference's ROAR and MaskGIT passes hand
+`forward_decoder` no self-attention mask (`sa_mask=None`, :644, :761; `forward_mask_decoder_{maskgit,roar}` :447-516 build none),
+so the flag only shapes the training forward.
 """
 from __future__ import annotations
 

@@ -82,3 +82,27 @@ class UnifiedMasking:
             ops.clip_synth(pkd, pkd, k_in[j], k_tg[j], n, 1, None, in_mask, tg_mask, dam)
             out[name] = {"tensor": t, "input_mask": in_mask, "target_mask": tg_mask, "decoder_attention_mask": dam}
         return out
+
+
+def causal_decoder_intervals(mod_mask) -> Tuple[np.ndarray, np.ndarray]:
+    """Key intervals of the decoder's self-attention under `decoder_causal_mask=True`, on the host: the rule ego_compact_causal
+    applies on the device (csrc/embed.hip), restated in numpy for tests and tools.
+
+    mod_mask: int [B, M], the decoder's modality id per kept row, -1 on padding rows (`forward_mask_decoder`'s last output,
+    egom2p_model.py:398-444; valid rows come first and every modality's rows are contiguous).  Returns (ks, ke) int32 [B, M]: valid
+    row r whose modality's rows start at g0 sees the keys [g0, r + 1) - `triu(1) | (mod_mask differs)` of
+    adapt_decoder_attention_mask (:459-463, 476-479); a padding row, which nothing consumes, gets every valid key [0, n_valid)."""
+    mm = np.asarray(mod_mask).astype(np.int64)
+    B, M = mm.shape
+    ks, ke = np.zeros((B, M), np.int32), np.zeros((B, M), np.int32)
+    for b in range(B):
+        nv = int((mm[b] >= 0).sum())
+        g0 = 0
+        for r in range(M):
+            if mm[b, r] < 0:
+                ks[b, r], ke[b, r] = 0, nv
+                continue
+            if r > 0 and mm[b, r] != mm[b, r - 1]:
+                g0 = r
+            ks[b, r], ke[b, r] = g0, r + 1
+    return ks, ke

@@ -8,7 +8,9 @@ parameters are views into the engine's flat fp32 buffer (`.grad` views into the 
 buffer) and `forward` / `loss.backward()` run the hand-written HIP kernels.
 
 Scope: the SwiGLU / bias-free / LayerNorm(no-bias) variants with token
-modalities (`VideoToken*`, `GazeCamToken*` embeddings).  Other variants raise NotImplementedError.
+modalities (`VideoToken*`, `GazeCamToken*` embeddings), with the standard or the causal decoder mask (`decoder_causal_mask`,
+always with `decoder_sep_mask=True`); `forward` takes a `mod_dict` holding any non-empty subset of the configured modalities.
+Other variants raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -139,7 +141,8 @@ class EgoM2P(nn.Module):
         if not gated_mlp or act_layer is not nn.SiLU: unsupported.append("non-SwiGLU MLP")
         if getattr(probe, "has_bias", True): unsupported.append("LayerNorm bias")
         if qk_norm: unsupported.append("qk_norm")
-        if decoder_causal_mask or not decoder_sep_mask: unsupported.append("causal / non-separated decoder mask")
+        # (decoder_causal_mask=True is supported together with the modality separation: one key interval per decoder row)
+        if not decoder_sep_mask: unsupported.append("decoder_sep_mask=False")
         if drop_path_rate_encoder or drop_path_rate_decoder: unsupported.append("drop path")
         if not share_modality_embeddings: unsupported.append("unshared modality embeddings")
         if set(encoder_embeddings) != set(decoder_embeddings): unsupported.append("different encoder/decoder modality sets")
@@ -167,7 +170,7 @@ class EgoM2P(nn.Module):
         self._mods = mods
         self.cfg = ModelCfg("custom", dim, encoder_depth, decoder_depth, num_heads, mlp_ratio,
                             modalities=tuple(m.name for m in mods), share_embedding=share, eps=probe.eps,
-                            num_register_tokens=int(num_register_tokens))
+                            num_register_tokens=int(num_register_tokens), decoder_causal_mask=bool(decoder_causal_mask))
         # ModelCfg.mods looks names up in MODALITIES: custom vocab / positions go through a private table
         self._device = device or ("cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else None)
         if self._device is None:
@@ -332,11 +335,18 @@ class EgoM2P(nn.Module):
                 loss_type: str = "mod", return_logits: bool = False):
         if loss_type not in ("mod", "modality", "weighted_mod", "token"):
             raise ValueError("Invalid loss type")                        # egom2p_model.py:579
+        # the reference runs on whatever modalities the batch holds (egom2p_model.py:706-714: datasets without gaze or depth) and
+        # averages the loss over those; a key without an embedding raises, as its embedding lookup would
+        if not mod_dict:
+            raise ValueError("mod_dict is empty")
+        unknown = [k for k in mod_dict if k not in self.encoder_modalities]
+        if unknown:
+            raise KeyError(f"mod_dict holds modalities this model has no embeddings for: {unknown}")
         names = [m.name for m in self._mods if m.name in mod_dict]
-        if len(names) != len(self._mods):
-            raise NotImplementedError("every configured modality must be present in mod_dict")
         B = mod_dict[names[0]]["tensor"].shape[0]
-        self._ensure(B, num_encoder_tokens, num_decoder_tokens)
+        # (argsort(...)[:, :n] of the reference cannot keep more rows than the present modalities have positions)
+        t_present = sum(m.max_tokens for m in self._mods if m.name in mod_dict)
+        self._ensure(B, min(num_encoder_tokens, t_present), min(num_decoder_tokens, t_present))
         md = {}
         for n in names:
             d = mod_dict[n]
@@ -382,12 +392,15 @@ def create_model(model_name, pretrained=False, checkpoint_path="", **kwargs):
     return _model_entrypoints[model_name](**kwargs)
 
 
-def _swiglu_variant(dim, depth, heads):
+def _swiglu_variant(dim, depth, heads, **fixed):
     def fn(encoder_embeddings, decoder_embeddings, **kwargs):
-        return EgoM2P(encoder_embeddings=encoder_embeddings, decoder_embeddings=decoder_embeddings,
-                      encoder_depth=depth, decoder_depth=depth, dim=dim, num_heads=heads, mlp_ratio=4,
-                      qkv_bias=False, proj_bias=False, mlp_bias=False,
-                      norm_layer=partial(LayerNorm, eps=1e-6, bias=False), act_layer=nn.SiLU, gated_mlp=True, **kwargs)
+        # (keywords of the call win over the entry's own: the same registered variant at another width or depth, which parity
+        #  tests use; the reference's entries raise TypeError on a repeated keyword)
+        args = dict(encoder_depth=depth, decoder_depth=depth, dim=dim, num_heads=heads, mlp_ratio=4,
+                    qkv_bias=False, proj_bias=False, mlp_bias=False,
+                    norm_layer=partial(LayerNorm, eps=1e-6, bias=False), act_layer=nn.SiLU, gated_mlp=True, **fixed)
+        args.update(kwargs)
+        return EgoM2P(encoder_embeddings=encoder_embeddings, decoder_embeddings=decoder_embeddings, **args)
     return fn
 
 
@@ -399,6 +412,10 @@ for _n, _a in {"egom2p_tiny_6e_6d_swiglu_nobias": (384, 6, 6), "egom2p_small_8e_
     _f = _swiglu_variant(*_a)
     _f.__name__ = _n
     register_model(_f)
+# decoder_causal_mask=True (egom2p_model.py:1029-1051): decoder self-attention under triu(1) | modality separation
+_f = _swiglu_variant(768, 12, 12, decoder_causal_mask=True)
+_f.__name__ = "egom2p_base_12e_12d_swiglu_nobias_causal"
+register_model(_f)
 
 
 def _unsupported(name, why):
@@ -411,6 +428,6 @@ def _unsupported(name, why):
 for _n in ("egom2p_tiny_6e_6d_gelu", "egom2p_small_8e_8d_gelu", "egom2p_base_12e_12d_gelu", "egom2p_large_24e_24d_gelu",
            "egom2p_xlarge_24e_24d_gelu"):
     register_model(_unsupported(_n, "GELU / biased variant"))
-for _n in ("egom2p_base_12e_12d_swiglu_nobias_causal", "egom2p_base_12e_12d_swiglu_qknorm_nobias",
-           "egom2p_large_24e_24d_swiglu_qknorm_nobias", "egom2p_xlarge_24e_24d_swiglu_qknorm_nobias"):
-    register_model(_unsupported(_n, "causal / qk-norm variant"))
+for _n in ("egom2p_base_12e_12d_swiglu_qknorm_nobias", "egom2p_large_24e_24d_swiglu_qknorm_nobias",
+           "egom2p_xlarge_24e_24d_swiglu_qknorm_nobias"):
+    register_model(_unsupported(_n, "qk-norm variant"))

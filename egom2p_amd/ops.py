@@ -358,9 +358,12 @@ def adamw_step_gated(p, g, m, v, lr, wd, step, gate, beta1=0.9, beta2=0.95, eps=
                                         _p(sqnorm), int(zero_grad), _p(gate), _stream()), "ego_adamw_step_gated")
 
 
-def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0):
+def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0,
+            causal=False):
     """`out`: dict of preallocated tensors (ids_keep,pad,mod_mask,slot,local,tok,ks,ke,n_valid,seg,err), n_reg + n_keep entries per
-    sample (n_reg: register tokens in front of the kept rows, encoder only)."""
+    sample (n_reg: register tokens in front of the kept rows, encoder only).
+    causal (decoder side only): the key intervals of `decoder_causal_mask=True` (ego_compact_causal; masking.causal_decoder_intervals
+    states the rule on the host)."""
     d = L.CompactDesc()
     d.n_mods, d.n_keep, d.is_decoder, d.n_reg = len(masks), n_keep, int(is_decoder), int(n_reg)
     for i in range(len(masks)):
@@ -372,6 +375,9 @@ def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_
     for k in ("ids_keep", "pad", "mod_mask", "slot", "local", "tok", "ks", "ke", "n_valid", "seg", "err"):
         setattr(d, k, out[k].data_ptr())
     d.seg_bad = out["seg_bad"].data_ptr() if out.get("seg_bad") is not None else None
+    if causal:
+        check(L.load().ego_compact_causal(C.byref(d), B, _stream()), "ego_compact_causal")
+        return
     check(L.load().ego_compact(C.byref(d), B, _stream()), "ego_compact")
 
 

@@ -26,8 +26,9 @@ extern "C" {
  * ego_bias_grad and ego_embed_bwd a scratch buffer for their atomic-free reductions; 4: ego_layernorm_fwd / _bwd take the
  * row pitch `ld` beside the normalised width D; 5: ego_compact_desc grew `seg_bad`, ego_embed_bwd_desc `vocab`, ego_ce_bwd / ego_ce_fwd_bwd / ego_loss_finalize take loss weights; 6 (round 5): register tokens - ego_compact_desc grew `n_reg`,
  * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
- * ego_maskgit_positions / ego_maskgit_select; loaders must refuse other versions) */
-#define EGO_ABI_VERSION 8
+ * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; loaders must refuse other
+ * versions) */
+#define EGO_ABI_VERSION 9
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -85,6 +86,15 @@ typedef struct {
                                         count them: n_valid = n_reg + kept, [ks, ke) = [0, n_valid)                         */
 } ego_compact_desc;
 int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream);
+/* The decoder side under `decoder_causal_mask=True` (adapt_decoder_attention_mask, egom2p/models/egom2p_model.py:459-463,
+ * 476-479: triu(1) | modality separation; the registered variant egom2p_base_12e_12d_swiglu_nobias_causal, :1029-1051).  Same
+ * descriptor and outputs as ego_compact with is_decoder = 1 (required), except the key intervals: forward_mask_decoder
+ * (:398-444) keeps a modality's kept rows contiguous, so kept row r of a slot whose kept rows are [s0, s1) gets
+ * [ks, ke) = [s0, r + 1); `dam` is not read and `err` is never raised (a pad key has an index > r: none is visible).  Padding
+ * rows, which nothing consumes, get [0, n_valid).  seg_bad[b] is raised for every sample with a slot of more than one kept row
+ * (its rows do not share one interval: ego_attn_*_d64_seg must take the per-row path).  The reference adds register tokens on
+ * the encoder side only (:381-387): n_reg must be 0 here; the cross-attention keys (registers included) are not affected. */
+int ego_compact_causal(const ego_compact_desc* d, int B, hipStream_t stream);
 
 /* Fused embedding of the kept rows: x = token_row + (pos_row + mod_emb), emb = pos_row + mod_emb;
  * padding rows are zero.  Replaces the embedding modules' forward (encoder_embeddings.py:181-210,
