@@ -11,8 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EGOM2P_HIP_LIB", os.path.join(_HERE, "libegom2p_hip.so"))   # override: kernel experiments
 MAX_MODS = 8
 
-ABI_VERSION = 9          # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
-EPI_BF16, EPI_F32, EPI_RESID, EPI_BIAS_RESID = 0, 1, 2, 3
+ABI_VERSION = 10         # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
+EPI_BF16, EPI_F32, EPI_RESID, EPI_BIAS_RESID, EPI_BIAS_BF16 = 0, 1, 2, 3, 4
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -73,6 +73,9 @@ _SIGS = {
     "ego_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp, i64, vp, vp],
     "ego_layernorm_bwd_work_floats": [i32, i32],
     "ego_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp],
+    "ego_layernorm_bias_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp],
+    "ego_layernorm_bias_bwd_work_floats": [i32, i32],
+    "ego_layernorm_bias_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp],
     "ego_layernorm_fwd_multi": [vp, i32, vp, vp, vp, vp, i32, i32, i64, f32, vp],
     "ego_layernorm_bwd_multi_work_floats": [i32, i32, i32],
     "ego_layernorm_bwd_multi": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp],
@@ -101,6 +104,8 @@ _SIGS = {
     "ego_clip_synth": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "ego_swiglu_fwd": [vp, vp, i64, i32, vp],
     "ego_swiglu_bwd": [vp, vp, vp, i64, i32, vp],
+    "ego_gelu_fwd": [vp, vp, i64, i32, i64, i64, vp],
+    "ego_gelu_bwd": [vp, vp, vp, i64, i32, i64, i64, i64, vp],
     "ego_gemm_nt_swiglu_bwd": [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, vp],
     "ego_gemm_nt_swiglu_fwd": [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp],
     "ego_ce_fwd": [vp, i64, i32, vp, vp, i32, vp, vp, vp],

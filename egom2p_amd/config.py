@@ -46,7 +46,8 @@ for _i in range(6):
 
 @dataclass(frozen=True)
 class ModelCfg:
-    """Shape of one EgoM2P variant (SwiGLU, bias-free, LayerNorm(no bias, eps 1e-6))."""
+    """Shape of one EgoM2P variant.  The defaults are the SwiGLU / bias-free / LayerNorm(no bias, eps 1e-6) family; `mlp="gelu"`
+    and the four bias flags describe the 4M-style default architecture of the `*_gelu` registrations (egom2p_model.py:881-978)."""
     name: str
     dim: int
     encoder_depth: int
@@ -58,6 +59,11 @@ class ModelCfg:
     eps: float = 1e-6
     num_register_tokens: int = 0       # learned [1, R, dim] rows in front of every sample's encoder tokens (egom2p_model.py:170-171, 381-387)
     decoder_causal_mask: bool = False  # decoder self-attention under triu(1) | modality separation (egom2p_model.py:459-463, 1029-1051)
+    mlp: str = "swiglu"                # "swiglu": GatedMlp (egom2p_utils.py:154-169); "gelu": Mlp, fc2(gelu(fc1 x)) with int(dim * mlp_ratio) hidden (:136-151)
+    qkv_bias: bool = False             # bias of qkv / q / kv (Attention / CrossAttention, egom2p_utils.py:172-244)
+    proj_bias: bool = False            # bias of the attention output projections
+    mlp_bias: bool = False             # bias of fc1 / fc2
+    norm_bias: bool = False            # LayerNorm with its bias (nn.LayerNorm; egom2p_utils.py:118-133)
 
     @property
     def head_dim(self) -> int:
@@ -65,7 +71,9 @@ class ModelCfg:
 
     @property
     def mlp_hidden(self) -> int:
-        # GatedMlp: int(2 * int(dim * mlp_ratio) / 3)  (reference `egom2p_utils.py:161,349`)
+        # GatedMlp: int(2 * int(dim * mlp_ratio) / 3)  (reference `egom2p_utils.py:161,349`); Mlp: int(dim * mlp_ratio) (:343-347)
+        if self.mlp == "gelu":
+            return int(self.dim * self.mlp_ratio)
         return int(2 * int(self.dim * self.mlp_ratio) / 3)
 
     @property
@@ -97,6 +105,11 @@ MODEL_CFGS: Dict[str, ModelCfg] = {
     # `decoder_causal_mask=True` (the registered egom2p_base_12e_12d_swiglu_nobias_causal, egom2p_model.py:1029-1051) at the tiny
     # variant's width (dim 384, 6 heads of 64) and parity-test depth: tests/golden/b2_causal.npz, b2_subset.npz
     "ego_384_2e_2d_causal": ModelCfg("ego_384_2e_2d_causal", 384, 2, 2, 6, decoder_causal_mask=True),
+    # the GELU / biased family (egom2p_tiny_6e_6d_gelu, egom2p_model.py:881-899: qkv / proj / mlp biases, nn.LayerNorm with bias, plain Mlp
+    # under an erf GELU, hidden 4 dim) at the tiny variant's width and parity-test depth: tests/golden/b2_gelu.npz, gen_rgb2depth_gelu.npz
+    "ego_384_2e_2d_gelu": ModelCfg("ego_384_2e_2d_gelu", 384, 2, 2, 6, mlp="gelu", qkv_bias=True, proj_bias=True, mlp_bias=True, norm_bias=True),
+    "ego_gen_384_2e_2d_gelu": ModelCfg("ego_gen_384_2e_2d_gelu", 384, 2, 2, 6, modalities=("tok_rgb", "tok_depth"), mlp="gelu",
+                                       qkv_bias=True, proj_bias=True, mlp_bias=True, norm_bias=True),
     "ego_L_1152": ModelCfg("ego_L_1152", 1152, 24, 24, 18),
     "ego_L_1152_2e_2d": ModelCfg("ego_L_1152_2e_2d", 1152, 2, 2, 18),       # ego-L width (BASELINE config 5) at parity-test depth
     # the REGISTERED ego-L geometry (egom2p_model.py:1080-1092: dim 1020, 15 heads of 68, F = 2720) at parity-test depth;

@@ -43,6 +43,16 @@ struct NTArgs {
 constexpr int EPI_SWIGLU_FWD = 101;   // internal: C = ab [M, 2N] and H = bf16(bf16(silu(a)) * b) [M, N] from one 256 x (128 a + 128 b) tile
 constexpr int EPI_SWIGLU_BWD = 100;   // internal: C(bf16)[M, 2N] = SwiGLU backward of (acc rounded to bf16) against X
 
+// EGO_EPI_BIAS_BF16: v + bias[gn .. gn + 3] in fp32 (the bias in its bf16 image, as autocast hands it to the linear - the rule of
+// EGO_EPI_BIAS_RESID); the caller rounds the sum to bf16 once.  Columns at or past N (a ragged last column tile) are never stored.
+__device__ __forceinline__ f32x4 add_bias4(f32x4 v, const float* __restrict__ bias, int gn, int N) {
+    if (gn < N) {
+        const f32x4 b = *(const f32x4*)(bias + gn);
+        v = f32x4{v[0] + round_bf16(b[0]), v[1] + round_bf16(b[1]), v[2] + round_bf16(b[2]), v[3] + round_bf16(b[3])};
+    }
+    return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // NT kernel, persistent.  Each workgroup walks a strided list of 128x128 output tiles; the K loop runs
 // as ONE pipeline across tile boundaries (the first K-step of the next tile is loaded under the last
@@ -51,6 +61,9 @@ constexpr int EPI_SWIGLU_BWD = 100;   // internal: C(bf16)[M, 2N] = SwiGLU backw
 // workgroups that share an XCD's L2 work on 64 consecutive tiles (same A row panel / neighbouring B
 // panels) - speed only, never correctness.
 // ---------------------------------------------------------------------------------------------
+// BIASB: the EGO_EPI_BIAS_BF16 epilogue, C(bf16) = bf16(acc + bias[n]) - an instantiation of its own, so that the code of the
+// bias-free one (every launch of the SwiGLU / no-bias family) is what it was
+template <bool BIASB = false>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NTArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -145,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NTArgs p) {
         // contiguous rows (4 rows x 256 B) instead of 16 scattered 32-byte pieces - on the K = 768 shapes the
         // scattered form cost ~30 % of the kernel.  16-byte chunk c of tile row r sits at chunk c ^ (r & 15).
         const int row0 = (tile / tiles_n) * BM, col0 = (tile % tiles_n) * BN;
-        if (p.epi == EGO_EPI_BF16) {
+        if (BIASB || p.epi == EGO_EPI_BF16) {
             // stage `cur` holds the next tile's K-step 0; put its K-step 1 in flight NOW (stage cur^1 is free)
             // and run the epilogue through the dedicated scratch, two 64-row halves of 16 KiB
             if (more && nt >= 2) {
@@ -163,7 +176,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NTArgs p) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int slot = wn * 16 + j * 4 + (lane >> 4);      // 8-byte slot (4 bf16) in the row
-                            const f32x4 v = acc[i][j];
+                            f32x4 v = acc[i][j];
+                            if constexpr (BIASB) v = add_bias4(v, p.bias, col0 + slot * 4, p.N);
                             u32x2 o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
                             *(u32x2*)(ebuf + ml * 256 + (((slot >> 1) ^ (ml & 15)) << 4) + (slot & 1) * 8) = o;
                         }
@@ -255,7 +269,7 @@ constexpr int NTL128x128_LDS = NTL<128, 128, 3>::LDS;   // 96 KiB: one workgroup
 template <int N>
 __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <int TM, int TN, int NS>
+template <int TM, int TN, int NS, bool BIASB = false>   // BIASB: EGO_EPI_BIAS_BF16 (see gemm_nt_kernel)
 __global__ __launch_bounds__(256, (NTL<TM, TN, NS>::LDS <= 80 * 1024 ? 2 : 1)) void gemm_ntl_kernel(NTArgs p) {
     using T = NTL<TM, TN, NS>;
     constexpr int MI = TM / 32, NI = TN / 32;                 // 16 x 16 accumulator blocks of a wave: (TM / 2) x (TN / 2) outputs
@@ -347,7 +361,8 @@ __global__ __launch_bounds__(256, (NTL<TM, TN, NS>::LDS <= 80 * 1024 ? 2 : 1)) v
             if (gm >= M || gn >= p.N) continue;
             const long mrow = moff + gm;
             f32x4 v = acc[i][j];
-            if (p.epi == EGO_EPI_BF16) {
+            if constexpr (BIASB) v = add_bias4(v, p.bias, gn, p.N);
+            if (BIASB || p.epi == EGO_EPI_BF16) {
                 *(u32x2*)((bf16_t*)p.C + mrow * p.ldc + gn) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
                 continue;
             }
@@ -431,7 +446,7 @@ __device__ __forceinline__ i32x8 cat_frag(bf16x8 lo, bf16x8 hi) {
 }
 
 // STRIPS: the column-strip tile walk of very wide outputs (its own instantiation: the narrow shapes keep the row-major code as is)
-template <int EK, bool FP8 = false, bool STRIPS = false>   // epilogue class: 0 bf16, 1 fp32 family, 2 fused SwiGLU backward, 3 fused SwiGLU forward (separate register allocations)
+template <int EK, bool FP8 = false, bool STRIPS = false>   // epilogue class: 0 bf16, 1 fp32 family, 2 fused SwiGLU backward, 3 fused SwiGLU forward, 4 bf16 + bias (separate register allocations)
 __global__ __launch_bounds__(512, 2) void gemm_nt256_kernel(NTArgs p) {
     constexpr int ESZ = FP8 ? 1 : 2;                           // bytes per operand element
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -669,7 +684,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_kernel(NTArgs p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) acc[i][j] = acc[i][j] * (cb[j] * ra[i]);
         }
-        if constexpr (EK == 0) {
+        if constexpr (EK == 0 || EK == 4) {
+            if constexpr (EK == 4) {          // EGO_EPI_BIAS_BF16: this lane's 4 x 4 columns of the tile, one load each for all 8 row blocks
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                    const f32x4 bj = add_bias4(z, p.bias, col0 + wc * 64 + j * 16 + (lane >> 4) * 4, p.N);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc[i][j] = acc[i][j] + bj;
+                }
+            }
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 if (grp == half) {
@@ -1292,7 +1316,13 @@ int g_ntl_tiles = 0;         // NT launches of at most this many 128 x 128 tiles
 bool g_attr_done = false;
 void ensure_attrs() {
     if (g_attr_done) return;
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS);
+    // the EGO_EPI_BIAS_BF16 instantiations
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_ntl_kernel<64, 64, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NT64_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_ntl_kernel<128, 64, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NTL128x64_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_ntl_kernel<128, 128, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NTL128x128_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, NT3_LDS);
     (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT64_LDS);
     (void)hipFuncSetAttribute((const void*)gemm_ntl_kernel<128, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, NTL128x64_LDS);
     (void)hipFuncSetAttribute((const void*)gemm_ntl_kernel<128, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, NTL128x128_LDS);
@@ -1350,10 +1380,13 @@ extern "C" int ego_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb
                                 const float* R, long ldr, const float* bias, const int* m_range,
                                 int M, int N, int K, int epi, hipStream_t stream) {
     if (M <= 0 || N <= 0) return EGO_OK;
-    if (K <= 0 || K % BK || N % 8 || lda % 8 || ldb % 8 || ldc % 4 || epi < 0 || epi > EGO_EPI_BIAS_RESID) return EGO_ERR_ARG;
-    if (epi == EGO_EPI_BF16 && ldc % 8) return EGO_ERR_ARG;
+    if (K <= 0 || K % BK || N % 8 || lda % 8 || ldb % 8 || ldc % 4 || epi < 0 || epi > EGO_EPI_BIAS_BF16) return EGO_ERR_ARG;
+    const bool bf16c = epi == EGO_EPI_BF16 || epi == EGO_EPI_BIAS_BF16;       // bf16 output: the same tile family with or without the bias
+    const bool biasb = epi == EGO_EPI_BIAS_BF16;
+    if (bf16c && ldc % 8) return EGO_ERR_ARG;
     if ((epi == EGO_EPI_RESID || epi == EGO_EPI_BIAS_RESID) && (!R || ldr % 4)) return EGO_ERR_ARG;
     if (epi == EGO_EPI_BIAS_RESID && !bias) return EGO_ERR_ARG;
+    if (biasb && (!bias || (((uintptr_t)bias) & 15))) return EGO_ERR_ARG;
     ensure_attrs();
     NTArgs a{(const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, R, ldr, bias, m_range, M, N, K, epi, nullptr, 0, nullptr, 0, nullptr, nullptr, g_nt_dephase};
     const int tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
@@ -1367,6 +1400,7 @@ extern "C" int ego_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb
         if (epi == EGO_EPI_BF16 && NT256_STRIPS && (N + 255) / 256 >= 32) {              // the 64,000-token logits: column-strip walk
             EGO_LAUNCH((gemm_nt256_kernel<0, false, true>), dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a);
         } else if (epi == EGO_EPI_BF16) { EGO_LAUNCH(gemm_nt256_kernel<0>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
+        else if (biasb) { EGO_LAUNCH(gemm_nt256_kernel<4>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
         else { EGO_LAUNCH(gemm_nt256_kernel<1>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
         LAUNCH_CHECK();
         return EGO_OK;
@@ -1384,36 +1418,41 @@ extern "C" int ego_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb
     //     5120 rows 320 tiles = two rounds against three (45 vs 41 us: the 128 x 128 kernel stays).
     // Device-side row ranges (m_range: the host M is only an upper bound) keep the round-4 choice.
     if (g_nt256 == 1 && g_ntl_force == 0 && g_ntl_tiles == 0 && !m_range && g_nt64_tiles == 400) {
-        const bool narrow = N <= 768 || epi != EGO_EPI_BF16;
+        const bool narrow = N <= 768 || !bf16c;
         int pick = 0;                                   // 0: round-4 rule below, 1: 64 x 64, 2: 128 x 64, 3: 256 x 256
         if (narrow) pick = tiles <= 100 ? 1 : tiles <= 520 ? 2 : 0;
         else if (tiles <= 330) pick = 2;
         else if (legal256 && 185 * ((tiles256 + 255) / 256) <= 100 * ((tiles + 511) / 512)) pick = 3;
         if (pick == 1) {
-            EGO_LAUNCH(gemm_nt64_kernel, dim3(((M + 63) / 64) * ((N + 63) / 64)), dim3(256), NT64_LDS, stream, a);
+            if (biasb) { EGO_LAUNCH((gemm_ntl_kernel<64, 64, 4, true>), dim3(((M + 63) / 64) * ((N + 63) / 64)), dim3(256), NT64_LDS, stream, a); }
+            else { EGO_LAUNCH(gemm_nt64_kernel, dim3(((M + 63) / 64) * ((N + 63) / 64)), dim3(256), NT64_LDS, stream, a); }
             LAUNCH_CHECK();
             return EGO_OK;
         }
         if (pick == 2) {
-            EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a);
+            if (biasb) { EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3, true>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a); }
+            else { EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a); }
             LAUNCH_CHECK();
             return EGO_OK;
         }
         if (pick == 3) {
             if (epi == EGO_EPI_BF16) { EGO_LAUNCH(gemm_nt256_kernel<0>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
+            else if (biasb) { EGO_LAUNCH(gemm_nt256_kernel<4>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
             else { EGO_LAUNCH(gemm_nt256_kernel<1>, dim3(tiles256 < 256 ? tiles256 : 256), dim3(512), NT3_LDS, stream, a); }
             LAUNCH_CHECK();
             return EGO_OK;
         }
     }
     if (g_ntl_force == 2) {
-        EGO_LAUNCH((gemm_ntl_kernel<128, 128, 3>), dim3(tiles), dim3(256), NTL128x128_LDS, stream, a);
+        if (biasb) { EGO_LAUNCH((gemm_ntl_kernel<128, 128, 3, true>), dim3(tiles), dim3(256), NTL128x128_LDS, stream, a); }
+        else EGO_LAUNCH((gemm_ntl_kernel<128, 128, 3>), dim3(tiles), dim3(256), NTL128x128_LDS, stream, a);
         LAUNCH_CHECK();
         return EGO_OK;
     }
     if (g_ntl_force == 1 || (tiles > g_nt64_tiles && tiles <= g_ntl_tiles)) {
         // one to a few rounds of 128 x 128 tiles (the generation path's encoder linears): 128 x 64 tiles on a 3-deep ring
-        EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a);
+        if (biasb) { EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3, true>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a); }
+        else EGO_LAUNCH((gemm_ntl_kernel<128, 64, 3>), dim3(((M + 127) / 128) * ((N + 63) / 64)), dim3(256), NTL128x64_LDS, stream, a);
         LAUNCH_CHECK();
         return EGO_OK;
     }
@@ -1421,11 +1460,13 @@ extern "C" int ego_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb
     // With a device-side row range the host M is only an upper bound: the grid is sized for it, surplus workgroups exit.
     if (g_nt64_tiles > 0 && tiles <= g_nt64_tiles) {
         const int tiles64 = ((M + 63) / 64) * ((N + 63) / 64);
-        EGO_LAUNCH(gemm_nt64_kernel, dim3(tiles64), dim3(256), NT64_LDS, stream, a);
+        if (biasb) { EGO_LAUNCH((gemm_ntl_kernel<64, 64, 4, true>), dim3(tiles64), dim3(256), NT64_LDS, stream, a); }
+        else EGO_LAUNCH(gemm_nt64_kernel, dim3(tiles64), dim3(256), NT64_LDS, stream, a);
         LAUNCH_CHECK();
         return EGO_OK;
     }
-    EGO_LAUNCH(gemm_nt_kernel, dim3(tiles < NT_WGS ? tiles : NT_WGS), dim3(256), NT_LDS, stream, a);
+    if (biasb) { EGO_LAUNCH(gemm_nt_kernel<true>, dim3(tiles < NT_WGS ? tiles : NT_WGS), dim3(256), NT_LDS, stream, a); }
+    else EGO_LAUNCH(gemm_nt_kernel<false>, dim3(tiles < NT_WGS ? tiles : NT_WGS), dim3(256), NT_LDS, stream, a);
     LAUNCH_CHECK();
     return EGO_OK;
 }

@@ -26,12 +26,14 @@ constexpr int LN_MAXC_MAX = 8;   // float4 chunks per lane -> D <= 2048 (kernels
 // ---------------------------------------------------------------------------------------------
 // LayerNorm forward: y(bf16) = (x - mean) * rstd * w ; optional output row permutation
 // ---------------------------------------------------------------------------------------------
-template <int LN_MAXC, bool TAIL>   // TAIL: D % 4 != 0 - the last chunk holds pad columns, masked element-wise
+// BIAS (ego_layernorm_bias_fwd): y = bf16(xhat * w + b), nn.LayerNorm with its bias; an instantiation of its own - the bias-free
+// one is the code it was
+template <int LN_MAXC, bool TAIL, bool BIAS = false>   // TAIL: D % 4 != 0 - the last chunk holds pad columns, masked element-wise
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      bf16_t* __restrict__ y, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, const int* __restrict__ out_row,
                                                      int rows, int D, int ld, float eps, unsigned char* __restrict__ q8, long ldq,
-                                                     float* __restrict__ qscale) {
+                                                     float* __restrict__ qscale, const float* __restrict__ b = nullptr) {
     // (no fma contraction anywhere in the LayerNorm kernels: the single-layer and the multi-layer kernels must agree bit for bit
     // whatever hipcc packs or fuses in one instantiation and not in another)
 #pragma clang fp contract(off)
@@ -75,9 +77,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
         const int c = lane + 64 * i;
         if (c < nc) {
             const f32x4 ww = *(const f32x4*)(w + c * 4);
+            f32x4 bb = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (BIAS) bb = *(const f32x4*)(b + c * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                v[i][e] = (!TAIL || c * 4 + e < D) ? round_bf16((v[i][e] - mean) * rstd * ww[e]) : 0.f;
+                if constexpr (BIAS) v[i][e] = (!TAIL || c * 4 + e < D) ? round_bf16((v[i][e] - mean) * rstd * ww[e] + bb[e]) : 0.f;
+                else v[i][e] = (!TAIL || c * 4 + e < D) ? round_bf16((v[i][e] - mean) * rstd * ww[e]) : 0.f;
                 amax = fmaxf(amax, fabsf(v[i][e]));
             }
             u32x2 o = {pack_bf16x2(v[i][0], v[i][1]), pack_bf16x2(v[i][2], v[i][3])};
@@ -112,7 +117,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 constexpr int LNB_ROWS = 32;   // rows per workgroup (8 per wave)
 
 // (second launch-bound argument = waves per SIMD the register allocation must allow: the kernel lives on the rows it has in flight)
-template <int LN_MAXC, bool TAIL>
+// BIAS (ego_layernorm_bias_bwd): also db = sum_rows dy - the workgroup's partial row is [dw | db], 2 D floats
+template <int LN_MAXC, bool TAIL, bool BIAS = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const int* __restrict__ dy_row,
                                                      const float* __restrict__ x, const float* __restrict__ mean_in,
                                                      const float* __restrict__ rstd_in, const float* __restrict__ w,
@@ -124,11 +130,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     __shared__ float red[4][LN_MAXC * 64 * 4];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform: row offsets / statistics stay scalar)
     const int nc = (D + 3) >> 2, ncl = ld >> 2;      // D = normalised width, ld = row pitch (columns [D, ld): zero gradient)
-    f32x4 ww[LN_MAXC], dwa[LN_MAXC];
+    f32x4 ww[LN_MAXC], dwa[LN_MAXC], dba[BIAS ? LN_MAXC : 1];
 #pragma unroll
     for (int i = 0; i < LN_MAXC; ++i) {
         const int c = lane + 64 * i;
         dwa[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (BIAS) dba[i] = dwa[i];
         ww[i] = (c < nc) ? *(const f32x4*)(w + c * 4) : dwa[i];
     }
     // (one row at a time per wave, no unrolling across rows: with the row loop unrolled hipcc kept two rows' registers alive - 122 /
@@ -174,6 +181,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                     const float xh = (xv[i][e] - mean) * rstd;
                     const float ge = d[e] * ww[i][e];
                     dwa[i][e] += d[e] * xh;
+                    if constexpr (BIAS) dba[i][e] += d[e];
                     s1 += ge;
                     s2 += ge * xh;
                 }
@@ -221,8 +229,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     __syncthreads();
     // one partial row per workgroup, plain stores (no float atomics: the sum over workgroups is taken in a fixed order by
     // colsum_kernel, so the weight gradient is bitwise reproducible - and the 768 same-address atomics per workgroup are gone)
+    const int pw = BIAS ? 2 * D : D;
     for (int col = threadIdx.x; col < D; col += 256)
-        dw_part[(long)blockIdx.x * D + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
+        dw_part[(long)blockIdx.x * pw + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
+    if constexpr (BIAS) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < LN_MAXC; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nc) *(f32x4*)(&red[wave][c * 4]) = dba[i];
+        }
+        __syncthreads();
+        for (int col = threadIdx.x; col < D; col += 256)
+            dw_part[(long)blockIdx.x * pw + D + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -507,6 +527,51 @@ __global__ void swiglu_bwd_kernel(const bf16_t* __restrict__ ab, const bf16_t* _
 }
 
 // ---------------------------------------------------------------------------------------------
+// GELU (erf form) of the biased MLP's pre-activation u[rows, F] (row pitches ld_*): h = bf16(u/2 * (1 + erf(u / sqrt 2))) in
+// fp32, and its autograd du = bf16(dh * (Phi(u) + u phi(u))) on the stored bf16 u.  HBM-bound: 4 / 6 B per element.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float gelu_f(float x) {
+    const float s = 1.f + erff(x * 0.70710678118654752440f);
+    // (Phi = 0 in fp32 from about -5.6 down: -0 like the product gives - also at -inf, where the product would be inf * 0)
+    return s == 0.f ? -0.f : (x * 0.5f) * s;
+}
+__device__ __forceinline__ float dgelu_f(float x) {
+    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
+    const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;          // phi(u) = exp(-u^2 / 2) / sqrt(2 pi)
+    return isinf(x) ? cdf : cdf + x * pdf;                                   // (+-inf: inf * 0 - the derivative's limit is Phi)
+}
+
+__global__ void gelu_fwd_kernel(const bf16_t* __restrict__ u, bf16_t* __restrict__ hout, long rows, int F, long ld_u, long ld_h) {
+    const int fc = F >> 3;                      // 8-element chunks per row
+    const long total = rows * fc;
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long r = idx / fc; const int c = (int)(idx % fc) * 8;
+        const u32x4 a = *(const u32x4*)(u + r * ld_u + c);
+        u32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(gelu_f(bf16_to_f32(a[e] & 0xffff)), gelu_f(bf16_to_f32(a[e] >> 16)));
+        *(u32x4*)(hout + r * ld_h + c) = o;
+    }
+}
+
+__global__ void gelu_bwd_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ dh, bf16_t* __restrict__ du, long rows, int F,
+                                long ld_u, long ld_dh, long ld_du) {
+    const int fc = F >> 3;
+    const long total = rows * fc;
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long r = idx / fc; const int c = (int)(idx % fc) * 8;
+        const u32x4 a = *(const u32x4*)(u + r * ld_u + c);
+        const u32x4 g = *(const u32x4*)(dh + r * ld_dh + c);
+        u32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            o[e] = pack_bf16x2(bf16_to_f32(g[e] & 0xffff) * dgelu_f(bf16_to_f32(a[e] & 0xffff)),
+                               bf16_to_f32(g[e] >> 16) * dgelu_f(bf16_to_f32(a[e] >> 16)));
+        *(u32x4*)(du + r * ld_du + c) = o;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // weight cast: fp32 W[rows_src, cols] -> bf16 Wb[rows_dst(pad), ld_w] (rows >= rows_src zero) and
 // bf16 Wt[cols, ld_t] = W^T (columns >= rows_src zero up to rows_dst).  32x32 LDS transpose tiles.
 // ---------------------------------------------------------------------------------------------
@@ -744,7 +809,9 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(const float* __rest
 // db[col] += sum_rows g[row][col]   (bf16 g, fp32 accumulate).  A workgroup owns 256 rows; a thread sums 8 adjacent columns
 // (one 16-byte load per row) of every (256 / (D / 8))-th row, the row groups are combined in LDS, one partial row per
 // workgroup (no atomics: bitwise reproducible).
-__global__ __launch_bounds__(256) void bias_grad_kernel(const bf16_t* __restrict__ g, long rows, int D, float* __restrict__ db_part) {
+// Wider matrices (the biased family's 3 dim and 4 dim) go chunk by chunk: D = the chunk's width, ld = the pitch of g's rows and
+// ldp that of the partial rows (both the full width; g and db_part already point at the chunk's first column).
+__global__ __launch_bounds__(256) void bias_grad_kernel(const bf16_t* __restrict__ g, long rows, int D, float* __restrict__ db_part, long ld, long ldp) {
     extern __shared__ __attribute__((aligned(16))) float bg_sm[];      // [rgroups][D]
     const int nvec = D >> 3, rgroups = 256 / nvec;
     const int cv = threadIdx.x % nvec, rg = threadIdx.x / nvec;
@@ -754,7 +821,7 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const bf16_t* __restrict
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     if (rg < rgroups) {
         for (long r = r0 + rg; r < r1; r += rgroups) {
-            const u32x4 v = *(const u32x4*)(g + r * D + cv * 8);
+            const u32x4 v = *(const u32x4*)(g + r * ld + cv * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { acc[2 * e] += bf16_to_f32(v[e] & 0xffff); acc[2 * e + 1] += bf16_to_f32(v[e] >> 16); }
         }
@@ -765,7 +832,7 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const bf16_t* __restrict
     for (int c = threadIdx.x; c < D; c += 256) {
         float s = 0.f;
         for (int q = 0; q < rgroups; ++q) s += bg_sm[q * D + c];
-        db_part[(long)blockIdx.x * D + c] = s;              // summed over workgroups in order by colsum_kernel
+        db_part[(long)blockIdx.x * ldp + c] = s;            // summed over workgroups in order by colsum_kernel
     }
 }
 
@@ -873,6 +940,46 @@ extern "C" int ego_layernorm_bwd(const void* dy, const int* dy_row, const float*
     return EGO_OK;
 }
 
+// nn.LayerNorm WITH its bias (the GELU / biased family, egom2p_model.py:881-978: norm_layer = partial(nn.LayerNorm, eps=1e-6);
+// egom2p_utils.py:118-133): the contract of ego_layernorm_fwd / ego_layernorm_bwd plus b and db
+extern "C" int ego_layernorm_bias_fwd(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd,
+                                      const int* out_row, int rows, int D, long ld, float eps, hipStream_t stream) {
+    if (rows <= 0) return EGO_OK;
+    if (D <= 0 || ld % 4 || ld < D || ld > LN_MAXC_MAX * 256 || !b) return EGO_ERR_ARG;
+#define LN_FWD_(C, T) EGO_LAUNCH((ln_fwd_kernel<C, T, true>), dim3((rows + 3) / 4), dim3(256), 0, stream, x, w, (bf16_t*)y, mean, rstd, out_row, rows, D, (int)ld, eps, \
+                             (unsigned char*)nullptr, 0L, (float*)nullptr, b)
+#define LN_FWD(C) do { if (D % 4) LN_FWD_(C, true); else LN_FWD_(C, false); } while (0)
+    if (ld <= 768) LN_FWD(3); else if (ld <= 1024) LN_FWD(4); else if (ld <= 1536) LN_FWD(6); else LN_FWD(8);
+#undef LN_FWD_
+#undef LN_FWD
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" long ego_layernorm_bias_bwd_work_floats(int rows, int D) { return colsum_work_floats((rows + LNB_ROWS - 1) / LNB_ROWS, 2 * D); }
+
+extern "C" int ego_layernorm_bias_bwd(const void* dy, const int* dy_row, const float* x, const float* mean,
+                                      const float* rstd, const float* w, const float* dx_in, float* dx_out,
+                                      void* dx_bf16, float* dw, float* db, float* work, long work_floats, int rows, int D, long ld,
+                                      hipStream_t stream) {
+    if (rows <= 0) return EGO_OK;
+    if (D <= 0 || ld % 4 || ld < D || ld > LN_MAXC_MAX * 256 || !dw || !db || !work || work_floats < ego_layernorm_bias_bwd_work_floats(rows, D))
+        return EGO_ERR_ARG;
+    const int nwg = (rows + LNB_ROWS - 1) / LNB_ROWS;
+#define LN_BWD_(C, T) EGO_LAUNCH((ln_bwd_kernel<C, T, true>), dim3(nwg), dim3(256), 0, stream, (const bf16_t*)dy, \
+                       dy_row, x, mean, rstd, w, dx_in, dx_out, (bf16_t*)dx_bf16, work, rows, D, (int)ld)
+#define LN_BWD(C) do { if (D % 4) LN_BWD_(C, true); else LN_BWD_(C, false); } while (0)
+    if (ld <= 768) LN_BWD(3); else if (ld <= 1024) LN_BWD(4); else if (ld <= 1536) LN_BWD(6); else LN_BWD(8);
+#undef LN_BWD_
+#undef LN_BWD
+    LAUNCH_CHECK();
+    ColsumDst dst{};
+    dst.p[0] = dw; dst.p[1] = db; dst.seg = D;          // partial rows are [dw | db]: column c goes to p[c / D][c % D]
+    colsum_launch(work, nwg, 2 * D, dst, stream);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
 extern "C" int ego_layernorm_fwd_multi(const float* x, int n_layers, const float* const* w, void* const* y, float* mean, float* rstd,
                                        int rows, int D, long ld, float eps, hipStream_t stream) {
     if (rows <= 0 || n_layers <= 0) return EGO_OK;
@@ -940,6 +1047,24 @@ extern "C" int ego_swiglu_bwd(const void* ab, const void* dh, void* dab, long ro
     if (rows <= 0) return EGO_OK;
     if (F % 8) return EGO_ERR_ARG;
     EGO_LAUNCH(swiglu_bwd_kernel, dim3(grid_for(rows * (F / 8))), dim3(256), 0, stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab, rows, F);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" int ego_gelu_fwd(const void* u, void* h, long rows, int F, long ld_u, long ld_h, hipStream_t stream) {
+    if (rows <= 0) return EGO_OK;
+    if (F <= 0 || F % 8 || ld_u % 8 || ld_h % 8 || ld_u < F || ld_h < F || ((((uintptr_t)u) | ((uintptr_t)h)) & 15)) return EGO_ERR_ARG;
+    EGO_LAUNCH(gelu_fwd_kernel, dim3(grid_for(rows * (F / 8))), dim3(256), 0, stream, (const bf16_t*)u, (bf16_t*)h, rows, F, ld_u, ld_h);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" int ego_gelu_bwd(const void* u, const void* dh, void* du, long rows, int F, long ld_u, long ld_dh, long ld_du, hipStream_t stream) {
+    if (rows <= 0) return EGO_OK;
+    if (F <= 0 || F % 8 || ld_u % 8 || ld_dh % 8 || ld_du % 8 || ld_u < F || ld_dh < F || ld_du < F ||
+        ((((uintptr_t)u) | ((uintptr_t)dh) | ((uintptr_t)du)) & 15)) return EGO_ERR_ARG;
+    EGO_LAUNCH(gelu_bwd_kernel, dim3(grid_for(rows * (F / 8))), dim3(256), 0, stream, (const bf16_t*)u, (const bf16_t*)dh, (bf16_t*)du, rows, F,
+               ld_u, ld_dh, ld_du);
     LAUNCH_CHECK();
     return EGO_OK;
 }
@@ -1036,12 +1161,17 @@ extern "C" long ego_bias_grad_work_floats(long rows, int D) { return colsum_work
 
 extern "C" int ego_bias_grad(const void* g, long rows, int D, float* db, float* work, long work_floats, hipStream_t stream) {
     if (rows <= 0) return EGO_OK;
-    if (D % 8 || D > 2048 || (((uintptr_t)g) & 15) || !work || work_floats < ego_bias_grad_work_floats(rows, D)) return EGO_ERR_ARG;
-    const int rgroups = 256 / (D / 8);
+    if (D <= 0 || D % 8 || (((uintptr_t)g) & 15) || !work || work_floats < ego_bias_grad_work_floats(rows, D)) return EGO_ERR_ARG;
     const long nwg = (rows + 255) / 256;
-    EGO_LAUNCH(bias_grad_kernel, dim3((unsigned)nwg), dim3(256), (size_t)rgroups * D * sizeof(float), stream,
-               (const bf16_t*)g, rows, D, work);
-    LAUNCH_CHECK();
+    // a launch sums at most 2048 columns (one 16-byte load per thread and row, 8 KiB of LDS): wider matrices - qkv / fc1 of the
+    // biased family, 3 dim and 4 dim - are walked in column chunks into the same full-width partial rows
+    for (int c0 = 0; c0 < D; c0 += 2048) {
+        const int w = D - c0 < 2048 ? D - c0 : 2048;
+        const int rgroups = 256 / (w / 8);
+        EGO_LAUNCH(bias_grad_kernel, dim3((unsigned)nwg), dim3(256), (size_t)rgroups * w * sizeof(float), stream,
+                   (const bf16_t*)g + c0, rows, w, work + c0, (long)D, (long)D);
+        LAUNCH_CHECK();
+    }
     ColsumDst dst{};
     dst.p[0] = db; dst.seg = D;
     colsum_launch(work, nwg, D, dst, stream);

@@ -72,10 +72,11 @@ def _pad128(n: int) -> int:
 class _Lin:
     """One linear layer: master view [out, in] (possibly padded), bf16 W [out, in] and W^T [in, out]; with the fp8
     forward enabled also W as OCP e4m3 bytes with one fp32 scale per output channel."""
-    __slots__ = ("name", "w", "g", "wb", "wt", "out_f", "in_f", "w8", "s8", "wt8", "st8")
+    __slots__ = ("name", "w", "g", "wb", "wt", "out_f", "in_f", "w8", "s8", "wt8", "st8", "b", "gb")
 
-    def __init__(self, name, w, g, dev, fp8=False, fp8_bwd=False):
+    def __init__(self, name, w, g, dev, fp8=False, fp8_bwd=False, b=None, gb=None):
         self.name, self.w, self.g = name, w, g
+        self.b, self.gb = b, gb          # fp32 bias [out] and its gradient (the biased family), else None
         self.out_f, self.in_f = w.shape
         self.wb = torch.zeros(self.out_f, self.in_f, device=dev, dtype=BF16)
         self.wt = torch.zeros(self.in_f, self.out_f, device=dev, dtype=BF16)
@@ -125,6 +126,22 @@ class Engine:
         if self.padded and (fp8_forward or fp8_backward):
             raise L.EgoHipError("the fp8 GEMMs are built for the unpadded shapes (dim % 128 == 0, head_dim 64)")
         self.F, self.Fp = cfg.mlp_hidden, _pad128(cfg.mlp_hidden)
+        # the GELU / biased family (egom2p_model.py:881-978): plain Mlp under an erf GELU (one [F, D] fc1, no fc3), a bias on qkv / q /
+        # kv, on proj and on fc1 / fc2, nn.LayerNorm with its bias - each its own flag of the configuration
+        if cfg.mlp not in ("swiglu", "gelu"):
+            raise ValueError(f"ModelCfg.mlp must be 'swiglu' or 'gelu', not {cfg.mlp!r}")
+        self.gelu = cfg.mlp == "gelu"
+        self.norm_bias = bool(cfg.norm_bias)
+        self.lin_bias = dict(qkv=bool(cfg.qkv_bias), proj=bool(cfg.proj_bias), mlp=bool(cfg.mlp_bias))
+        family = self.gelu or self.norm_bias or any(self.lin_bias.values())
+        if family and (fp8_forward or fp8_backward):
+            raise NotImplementedError("the fp8 GEMMs carry no bias epilogue and the fp8 forward no GELU / biased LayerNorm: the GELU / "
+                                      "biased family (mlp='gelu', qkv_bias, proj_bias, mlp_bias, norm_bias) runs in bf16 only")
+        if family and self.padded:
+            raise NotImplementedError("the GELU / biased family is built for unpadded storage (dim % 128 == 0, heads of 64)")
+        if cfg.mlp_bias and not self.gelu:
+            raise NotImplementedError("mlp_bias with the gated MLP (a bias on the fused fc1||fc3 launch) is not built: mlp_bias needs mlp='gelu'")
+        self.Fab = self.Fp if self.gelu else 2 * self.Fp        # width of the saved MLP pre-activation rows: u, or a || b
         self.mods: List[Modality] = cfg.mods
         self.n_mods = len(self.mods)
         self.N, self.M, self.Bmax = n_enc, n_dec, max_batch
@@ -164,8 +181,9 @@ class Engine:
         self.gen_overlap = os.environ.get("EGOM2P_GEN_OVERLAP", "0") == "1"     # generation: independent launches on a second stream (_fork)
         # every decoder layer's context_norm normalises the SAME context tensor: one fused launch forward (x and its statistics
         # read once, one output per layer) and one backward (x once, one write of the context gradient) instead of one per layer
+        # (the multi-layer launches have no biased twin: with norm_bias every layer's context_norm is its own launch)
         self.ctx_ln_fused = (os.environ.get("EGOM2P_CTX_LN_FUSED", "1") != "0" and not self.fp8_forward and self.D <= 1536
-                             and 0 < cfg.decoder_depth <= 32)
+                             and 0 < cfg.decoder_depth <= 32 and not self.norm_bias)
 
     def layout_tag(self) -> Tuple[int, ...]:
         """What the PHYSICAL flat buffers (P, G and the optimiser's m / v) depend on beyond the model: saved with optimiser
@@ -213,9 +231,13 @@ class Engine:
         back (an MFMA-bound launch with no consumer before the next bucket boundary) beside it on a second stream: the GEMM
         starts when the LayerNorm does, and the main stream goes on only after both (two MFMA kernels never overlap: that was
         measured 5 - 26 % slower)."""
+        db = kw.pop("db", None)            # the norm's bias gradient (norm_bias): the biased entry
+        if db is not None:
+            a = a[:7] + (db,) + a[7:]
+        ln_bwd = ops.layernorm_bwd if db is None else ops.layernorm_bias_bwd
         run, self._pend = self._pend, None
         if run is None:
-            return ops.layernorm_bwd(*a, **kw)
+            return ln_bwd(*a, **kw)
         main = torch.cuda.current_stream()
         e0, e1 = self._pair_ev[self._pair_i], self._pair_ev[self._pair_i + 1]
         self._pair_i = (self._pair_i + 2) % len(self._pair_ev)
@@ -224,7 +246,7 @@ class Engine:
             self.pair_stream.wait_event(e0)
             run()
             e1.record(self.pair_stream)
-        ops.layernorm_bwd(*a, **kw)
+        ln_bwd(*a, **kw)
         main.wait_event(e1)
 
     # ------------------------------------------------------------------------------------ parameters
@@ -236,13 +258,25 @@ class Engine:
         def add(name, shape):
             spec.append((name, tuple(shape)))
 
+        def norm(name):           # a LayerNorm's weight and, with norm_bias, its bias (nn.LayerNorm's names)
+            add(f"{name}.weight", (D,))
+            if self.norm_bias:
+                add(f"{name}.bias", (D,))
+
         def layer(prefix, kind):
             # (a decoder layer's context_norm weight lives in the "ctx_norms" group in front of the decoder layers: with the fused
             #  context LayerNorm backward its gradient is only final after the LAST decoder layer's backward, and it must not
             #  hold the layer's 14 MB gradient bucket back from the data-parallel exchange until then - ADVICE r4)
             norms = ["norm1", "norm2"] if kind == "enc" else ["norm1", "query_norm", "norm2"]
             for n in norms:
-                add(f"{prefix}.{n}.weight", (D,))
+                norm(f"{prefix}.{n}")
+            # the linears' biases (reference names) sit behind the norms: one no-decay run per layer, in the layer's own bucket
+            lins = ([("attn.qkv", 3 * A, "qkv"), ("attn.proj", D, "proj")] if kind == "enc" else
+                    [("self_attn.qkv", 3 * A, "qkv"), ("self_attn.proj", D, "proj"), ("cross_attn.q", A, "qkv"),
+                     ("cross_attn.kv", 2 * A, "qkv"), ("cross_attn.proj", D, "proj")]) + [("mlp.fc1", Fp, "mlp"), ("mlp.fc2", D, "mlp")]
+            for sub, n, flag in lins:
+                if self.lin_bias[flag]:
+                    add(f"{prefix}.{sub}.bias", (n,))
             if kind == "enc":
                 add(f"{prefix}.attn.qkv.weight", (3 * A, D))
                 add(f"{prefix}.attn.proj.weight", (D, A))
@@ -253,7 +287,8 @@ class Engine:
                 add(f"{prefix}.cross_attn.kv.weight", (2 * A, D))
                 add(f"{prefix}.cross_attn.proj.weight", (D, A))
             add(f"{prefix}.mlp.fc1.weight", (Fp, D))      # fc1 | fc3 adjacent: one fused [2Fp, D] GEMM operand
-            add(f"{prefix}.mlp.fc3.weight", (Fp, D))
+            if not self.gelu:                             # (the plain Mlp has no fc3: egom2p_utils.py:136-151)
+                add(f"{prefix}.mlp.fc3.weight", (Fp, D))
             add(f"{prefix}.mlp.fc2.weight", (D, Fp))
 
         marks = []
@@ -269,18 +304,18 @@ class Engine:
             marks.append((f"encoder.{i}", len(spec)))
             layer(f"encoder.{i}", "enc")
         marks.append(("bridge", len(spec)))
-        add("encoder_norm.weight", (D,))
+        norm("encoder_norm")
         add("decoder_proj_context.bias", (D,))
         add("decoder_proj_context.weight", (D, D))
         if cfg.decoder_depth:
             marks.append(("ctx_norms", len(spec)))
             for i in range(cfg.decoder_depth):
-                add(f"decoder.{i}.context_norm.weight", (D,))
+                norm(f"decoder.{i}.context_norm")
         for i in range(cfg.decoder_depth):
             marks.append((f"decoder.{i}", len(spec)))
             layer(f"decoder.{i}", "dec")
         marks.append(("head", len(spec)))
-        add("decoder_norm.weight", (D,))
+        norm("decoder_norm")
         add("mask_token", (D,))
         for m in self.mods:
             marks.append((f"dec_table.{m.name}", len(spec)))
@@ -334,16 +369,19 @@ class Engine:
 
         def lin(name):
             body = "token_emb" not in name and "to_logits" not in name
-            self.lin[name] = _Lin(name, self.p[name], self.g[name], self.dev, fp8=self.fp8_forward and body, fp8_bwd=self.fp8_backward and body)
+            # a layer linear's own bias (the biased family); decoder_proj_context's bias is handed over by its call sites, as ever
+            bk = name[:-len("weight")] + "bias" if name.startswith(("encoder.", "decoder.")) else None
+            self.lin[name] = _Lin(name, self.p[name], self.g[name], self.dev, fp8=self.fp8_forward and body, fp8_bwd=self.fp8_backward and body,
+                                  b=self.p.get(bk), gb=self.g.get(bk))
 
         for i in range(cfg.encoder_depth):
             for s in ("attn.qkv", "attn.proj", "mlp.fc2"):
                 lin(f"encoder.{i}.{s}.weight")
-            self._fuse13(f"encoder.{i}")
+            lin(f"encoder.{i}.mlp.fc1.weight") if self.gelu else self._fuse13(f"encoder.{i}")
         for i in range(cfg.decoder_depth):
             for s in ("self_attn.qkv", "self_attn.proj", "cross_attn.q", "cross_attn.kv", "cross_attn.proj", "mlp.fc2"):
                 lin(f"decoder.{i}.{s}.weight")
-            self._fuse13(f"decoder.{i}")
+            lin(f"decoder.{i}.mlp.fc1.weight") if self.gelu else self._fuse13(f"decoder.{i}")
         lin("decoder_proj_context.weight")
         for m in self.mods:
             key = (f"decoder_embeddings.{m.name}.token_emb.weight" if cfg.share_embedding
@@ -363,8 +401,8 @@ class Engine:
     # reference key layout <-> engine storage ----------------------------------------------------
     def _view_for_key(self, key: str) -> Optional[torch.Tensor]:
         F, Fp = self.F, self.Fp
-        if key.endswith("pos_emb") or (key.endswith(".bias") and "norm" in key):
-            return None                                   # buffers: pos tables are rebuilt, LN bias is a zero buffer
+        if key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key):
+            return None                                   # buffers: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)
         k = key.replace("decoder_embeddings", "DE").replace("encoder_embeddings", "EE")
         if k.startswith("DE") and k.endswith("mod_emb"):
             key = key.replace("decoder_embeddings", "encoder_embeddings")      # shared Parameter
@@ -414,8 +452,8 @@ class Engine:
         `load_state_dict` reports them as unexpected / raises under strict=True)."""
         unexpected = []
         for key, val in sd.items():
-            if key.endswith("pos_emb") or (key.endswith(".bias") and "norm" in key):
-                continue                                  # buffers: pos tables are rebuilt, LN bias is a zero buffer
+            if key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key):
+                continue                                  # buffers: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)
             if self._canon_key(key) not in self.p:
                 unexpected.append(key)
                 continue
@@ -444,7 +482,7 @@ class Engine:
         for name in self.p:
             if name.startswith(("encoder.", "decoder.", "encoder_norm", "decoder_norm", "decoder_proj_context")):
                 out[name] = ref(name)
-                if name.endswith("norm.weight") or ".norm" in name or "norm1" in name or "norm2" in name:
+                if not self.norm_bias and (name.endswith("norm.weight") or ".norm" in name or "norm1" in name or "norm2" in name):
                     out[name[:-len("weight")] + "bias"] = zeros
         out["mask_token"] = ref("mask_token").view(1, 1, D)
         if self.R:
@@ -498,16 +536,25 @@ class Engine:
                 v.copy_((torch.rand(v.shape, device=self.dev, generator=gen) * 2 - 1) * a)
             elif name.endswith("token_emb.weight") or name.endswith("mod_emb") or name in ("mask_token", "register_tokens"):
                 v.copy_(torch.randn(v.shape, device=self.dev, generator=gen) * 0.02)
+            elif name.endswith(".bias"):
+                v.zero_()                                 # (the biased family's own biases: drawn below, from their own generator)
             elif name.endswith("norm.weight") or ".norm" in name:
                 v.fill_(1.0)
-            elif name.endswith(".bias"):
-                v.zero_()
             else:
                 fo, fi = self._ref_shape(name)
                 if "qkv" in name: fo //= 3
                 elif "kv" in name: fo //= 2
                 a = math.sqrt(6.0 / (fo + fi))
                 v.copy_((torch.rand(v.shape, device=self.dev, generator=gen) * 2 - 1) * a)
+        # the biases of the biased family: NON-zero (the reference's init zeroes them - EgoM2P.init_weights does that - but a zero
+        # bias hides a dead bias path from every test that starts here), from a generator of their own after all draws above, so
+        # that the stream the other tensors see does not depend on the flags
+        bgen = torch.Generator(device=self.dev)
+        bgen.manual_seed(seed + 0x5EED)
+        for name in self.p:
+            if name.endswith(".bias") and name != "decoder_proj_context.bias":
+                v = self._view_for_key(name)
+                v.copy_(torch.randn(v.shape, device=self.dev, generator=bgen) * 0.05)
         self.weights_dirty = True
 
     def param_names(self) -> List[str]:
@@ -558,7 +605,7 @@ class Engine:
         def enc_layer():
             return dict(x=e(RN, D, dt=F32), xm=e(RN, D, dt=F32), ln1=e(RN, D), qkv=e(RN, 3 * A), ao=e(RN, A),
                         ao_lo=e(RN, A) if self.attn_o_residual == "all" else None,
-                        lse=e(B, H, N, dt=F32), st1=e(2, RN, dt=F32), ln2=e(RN, D), ab=e(RN, 2 * Fp), h=e(RN, Fp),
+                        lse=e(B, H, N, dt=F32), st1=e(2, RN, dt=F32), ln2=e(RN, D), ab=e(RN, self.Fab), h=e(RN, Fp),
                         st2=e(2, RN, dt=F32))
 
         def dec_layer():
@@ -567,7 +614,7 @@ class Engine:
                         st1=e(2, RM, dt=F32), qn=e(RM, D), q=e(RM, A),
                         stq=e(2, RM, dt=F32), cn=e(RN, D), kv=e(RN, 2 * A), stc=e(2, RN, dt=F32), xo=e(RM, A),
                         xo_lo=e(RM, A) if self.attn_o_residual != "none" else None,
-                        lse_x=e(B, H, M, dt=F32), ln2=e(RM, D), ab=e(RM, 2 * Fp), h=e(RM, Fp), st2=e(2, RM, dt=F32))
+                        lse_x=e(B, H, M, dt=F32), ln2=e(RM, D), ab=e(RM, self.Fab), h=e(RM, Fp), st2=e(2, RM, dt=F32))
 
         self.enc = [enc_layer() for _ in range(cfg.encoder_depth)]
         self.dec = [dec_layer() for _ in range(cfg.decoder_depth)]
@@ -605,7 +652,7 @@ class Engine:
         self.t_3d = e(R, 3 * A)
         self.t_2d = e(RN, 2 * A)
         self.t_f = e(R, Fp)
-        self.t_2f = e(R, 2 * Fp)
+        self.t_2f = e(R, self.Fab)
         self.dyn = torch.zeros(RM, D, device=dev, dtype=BF16)
         self.delta = e(B, H, max(N, M), dt=F32)
         self.slab = e(64 * 1024 * 1024 // 4, dt=F32)   # 64 MiB of split-K partials (256 workgroups x 256 KiB)
@@ -619,7 +666,10 @@ class Engine:
         """LayerNorm forward; with the fp8 forward on, the row also leaves as e4m3 (+ scale) for the GEMM that follows
         (no separate quantisation pass for the LayerNorm-fed linears)."""
         rows = x.shape[0]
-        if self.fp8_forward and out_row is None and self.D % 128 == 0 and self.D >= 256:
+        if self.norm_bias:            # nn.LayerNorm with its bias: the biased entry, once per layer
+            ops.layernorm_bias_fwd(x, self.p[wname], self.p[wname[:-len("weight")] + "bias"], y, st[0], st[1], out_row=out_row,
+                                   eps=self.cfg.eps, width=self.Dl)
+        elif self.fp8_forward and out_row is None and self.D % 128 == 0 and self.D >= 256:
             q = self._qbuf(rows, self.D)
             ops.layernorm_fwd(x, self.p[wname], y, st[0], st[1], eps=self.cfg.eps, q8=q, qscale=self.qs)
             self._q_of = (y.data_ptr(), rows, self.D)
@@ -644,6 +694,9 @@ class Engine:
 
     def _lin_fwd(self, name, A, C, rows, epi=L.EPI_BF16, R=None, bias=None):
         l = self.lin[name]
+        if l.b is not None:
+            # the linear's own bias: bf16(acc + bias) - qkv / q / kv / fc1 - or, in front of the residual add, proj / fc2
+            epi, bias = {L.EPI_BF16: L.EPI_BIAS_BF16, L.EPI_RESID: L.EPI_BIAS_RESID}[epi], l.b
         if l.w8 is not None and rows > 0:
             q = self._quant(A, rows, l.in_f)
             ops.gemm_nt_fp8(q, self.qs, l.w8, l.s8, C, rows, l.out_f, l.in_f, epi, R=R, bias=bias)
@@ -652,7 +705,12 @@ class Engine:
                     ldr=None if R is None else R.shape[-1])
 
     def _mlp_gate_fwd(self, pre, xn, ab, h, rows):
-        """ab = fc1||fc3(xn), h = silu(a) * b - one launch where the shape allows it"""
+        """ab = fc1||fc3(xn), h = silu(a) * b - one launch where the shape allows it; the plain Mlp: ab = u = fc1(xn) (+ bias), the
+        bf16 pre-activation the backward reads, h = gelu(u)"""
+        if self.gelu:
+            self._lin_fwd(f"{pre}.mlp.fc1.weight", xn, ab, rows)
+            ops.gelu_fwd(ab, h, rows, self.Fp)
+            return
         l = self.lin[f"{pre}.mlp.fc13"]
         if l.w8 is not None and rows > 0:
             q = self._quant(xn, rows, l.in_f)
@@ -667,8 +725,10 @@ class Engine:
             ops.swiglu_fwd(ab, h, rows, self.Fp)
 
     def _lin_bwd(self, name, dY, X, dX, rows):
-        """dX(bf16) = dY @ W ; dW += dY^T @ X."""
+        """dX(bf16) = dY @ W ; dW += dY^T @ X ; with a bias of its own db += column sums of the bf16 dY."""
         l = self.lin[name]
+        if l.gb is not None:
+            ops.bias_grad(dY, rows, l.out_f, l.gb)
         if dX is not None and l.wt8 is not None and rows > 0:
             q = self._quant(dY, rows, l.out_f)               # e4m3 rows of dY + per-row scales (one pass over dY)
             ops.gemm_nt_fp8(q, self.qs, l.wt8, l.st8, dX, rows, l.in_f, l.out_f, L.EPI_BF16)
@@ -871,8 +931,12 @@ class Engine:
             self._mlp_gate_fwd(pre, w["ln2"], w["ab"], w["h"], RM)
             self._lin_fwd(f"{pre}.mlp.fc2.weight", w["h"], nxt, RM, L.EPI_RESID, R=w["x2"])
         # decoder_norm, rows written modality-grouped (the row order of y[decoder_mod_mask == id], :633)
-        ops.layernorm_fwd(self.y_out[:RM], self.p["decoder_norm.weight"], self.yn, self.st_dn[0], self.st_dn[1],
-                          out_row=self.perm if group_rows else None, eps=cfg.eps, width=self.Dl)
+        if self.norm_bias:
+            ops.layernorm_bias_fwd(self.y_out[:RM], self.p["decoder_norm.weight"], self.p["decoder_norm.bias"], self.yn, self.st_dn[0],
+                                   self.st_dn[1], out_row=self.perm if group_rows else None, eps=cfg.eps, width=self.Dl)
+        else:
+            ops.layernorm_fwd(self.y_out[:RM], self.p["decoder_norm.weight"], self.yn, self.st_dn[0], self.st_dn[1],
+                              out_row=self.perm if group_rows else None, eps=cfg.eps, width=self.Dl)
         self._have_fwd = True
         if not need_loss:
             return None
@@ -906,17 +970,21 @@ class Engine:
         Fp = self.Fp
         dh, dab, dln = self.t_f, self.t_2f, self.t_d
         l2 = self.lin[f"{pre}.mlp.fc2.weight"]
-        if ops.swiglu_bwd_fusable(Fp, l2.out_f) and rows >= 4096:
+        if self.gelu:
+            # plain Mlp: dh = dY W2, du = dh * gelu'(u) on the stored bf16 pre-activation, then fc1 (their bias gradients: _lin_bwd)
+            self._lin_bwd(f"{pre}.mlp.fc2.weight", dres_b, w["h"], dh, rows)
+            ops.gelu_bwd(w["ab"], dh, dab, rows, Fp)
+        elif ops.swiglu_bwd_fusable(Fp, l2.out_f) and rows >= 4096:
             # fc2 dgrad and the gate backward in one launch (dh never reaches HBM), then the fc2 wgrad
             ops.gemm_nt_swiglu_bwd(dres_b, l2.wt, w["ab"], dab, rows, Fp, l2.out_f, ldy=dres_b.shape[-1], ldw=l2.out_f)
             self._wgrad(l2.g, dres_b, w["h"], l2.out_f, l2.in_f, rows, ldp=dres_b.shape[-1], ldq=w["h"].shape[-1])
         else:
             self._lin_bwd(f"{pre}.mlp.fc2.weight", dres_b, w["h"], dh, rows)
             ops.swiglu_bwd(w["ab"], dh, dab, rows, Fp)
-        self._lin_bwd(f"{pre}.mlp.fc13", dab, w["ln2"], dln, rows)
+        self._lin_bwd(f"{pre}.mlp.fc1.weight" if self.gelu else f"{pre}.mlp.fc13", dab, w["ln2"], dln, rows)
         nb = self._ring_next()
         self._ln_bwd(dln, xin[:rows], w["st2"][0], w["st2"][1], self.p[f"{pre}.norm2.weight"], dres, self.g[f"{pre}.norm2.weight"],
-                          dx_in=dres, dx_bf16=nb, width=self.Dl)
+                          dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.norm2.bias"))
         return nb
 
     def _self_attn_bwd(self, pre, attn_name, w, dres, dres_b, rows, Nq, ks, ke, r_bs=None, r_rs=1, groups=None):
@@ -929,7 +997,7 @@ class Engine:
         self._lin_bwd(f"{pre}.{attn_name}.qkv.weight", dqkv, w["ln1"], dln, rows)
         nb = self._ring_next()
         self._ln_bwd(dln, w["x"][:rows], w["st1"][0], w["st1"][1], self.p[f"{pre}.norm1.weight"], dres, self.g[f"{pre}.norm1.weight"],
-                          dx_in=dres, dx_bf16=nb, width=self.Dl)
+                          dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.norm1.bias"))
         return nb
 
     def _set_gscale(self, gscale):
@@ -976,8 +1044,13 @@ class Engine:
         for m in reversed(self.mods):                          # (every bucket is handed over, an absent modality's with zeros)
             done(f"dec_table.{m.name}" if cfg.share_embedding else f"to_logits.{m.name}")
         dres, dres_b = self.dres, self._ring_next()
-        ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
-                          self.g["decoder_norm.weight"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm, width=self.Dl)
+        if self.norm_bias:
+            ops.layernorm_bias_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
+                                   self.g["decoder_norm.weight"], self.g["decoder_norm.bias"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm,
+                                   width=self.Dl)
+        else:
+            ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
+                              self.g["decoder_norm.weight"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm, width=self.Dl)
 
         # ---- decoder layers
         first_ctx = True
@@ -995,13 +1068,14 @@ class Engine:
             self._lin_bwd(f"{pre}.cross_attn.q.weight", dq, w["qn"], dln, RM)
             nb = self._ring_next()
             self._ln_bwd(dln, w["x1"][:RM], w["stq"][0], w["stq"][1], self.p[f"{pre}.query_norm.weight"], dres,
-                              self.g[f"{pre}.query_norm.weight"], dx_in=dres, dx_bf16=nb, width=self.Dl)
+                              self.g[f"{pre}.query_norm.weight"], dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.query_norm.bias"))
             dres_b = nb
             dcn = self.dcn[i] if fused else self.t_d3    # not t_d2: dq is still being read by the q-projection wgrad on the side stream
             self._lin_bwd(f"{pre}.cross_attn.kv.weight", dkv, w["cn"], dcn, RN)
             if not fused:
                 self._ln_bwd(dcn, self.ctx[:RN], w["stc"][0], w["stc"][1], self.p[f"{pre}.context_norm.weight"], self.dctx,
-                                  self.g[f"{pre}.context_norm.weight"], dx_in=None if first_ctx else self.dctx, width=self.Dl)
+                                  self.g[f"{pre}.context_norm.weight"], dx_in=None if first_ctx else self.dctx, width=self.Dl,
+                                  db=self.g.get(f"{pre}.context_norm.bias"))
             first_ctx = False
             dres_b = self._self_attn_bwd(pre, "self_attn", w, dres, dres_b, RM, M, cd["ks"], cd["ke"], groups=self._dec_groups())
             done(pre)                 # (the layer's context_norm weight is not in this bucket: "ctx_norms")
@@ -1032,7 +1106,7 @@ class Engine:
         self._lin_bwd("decoder_proj_context.weight", self.dctx_b, self.xe, dxe_n, RN)
         dxe, dxe_b = self.dxe, self._ring_next()
         self._ln_bwd(dxe_n, self.x_enc_out[:RN], self.st_en[0], self.st_en[1], self.p["encoder_norm.weight"], dxe,
-                          self.g["encoder_norm.weight"], dx_in=None, dx_bf16=dxe_b, width=self.Dl)
+                          self.g["encoder_norm.weight"], dx_in=None, dx_bf16=dxe_b, width=self.Dl, db=self.g.get("encoder_norm.bias"))
         done("bridge")
 
         # ---- encoder layers
@@ -1111,7 +1185,7 @@ class Engine:
             groups=G, sides=[side() for _ in range(G)],
             xa=e(RE, D, dt=F32), xb=e(RE, D, dt=F32), emb=e(RE, D, dt=F32), ctx=e(RC, D, dt=F32),
             ya=e(RD, D, dt=F32), yb=e(RD, D, dt=F32),
-            ln=e(max(R, RC), D), qkv=e(R, 3 * A), ao=e(R, A), ab=e(R, 2 * Fp), h=e(R, Fp), q=e(RD, A), cn=e(RC, D),
+            ln=e(max(R, RC), D), qkv=e(R, 3 * A), ao=e(R, A), ab=e(R, self.Fab), h=e(R, Fp), q=e(RD, A), cn=e(RC, D),
             kv=e(RC, 2 * A), st=e(2, max(R, RC), dt=F32), lse=e(G * B, H, max(Nmax, Mmax), dt=F32),
             zero_b=torch.zeros(G * B, device=dev, dtype=I32), full_m=torch.zeros(G * B, device=dev, dtype=I32),
             dslot=torch.zeros(RD, device=dev, dtype=I32), dtok=torch.zeros(RD, device=dev, dtype=I32),
@@ -1228,6 +1302,7 @@ class Engine:
             self._lin_fwd(f"{pre}.self_attn.qkv.weight", w["ln"], w["qkv"], RD)
             self._attn_infer(w, w["qkv"], 0, 3 * A, w["qkv"], A, 2 * A, 3 * A, w["ao"], w["zero_b"], w["full_m"], G * B, M, M)
             self._lin_fwd(f"{pre}.self_attn.proj.weight", w["ao"], yn, RD, L.EPI_RESID, R=y)
+            proj_b = self.lin[f"{pre}.cross_attn.proj.weight"].b is not None
             if RQ > 0:
                 self._ln(yn[:RQ], f"{pre}.query_norm.weight", w["ln"], w["st"])
                 self._lin_fwd(f"{pre}.cross_attn.q.weight", w["ln"], w["q"], RQ)
@@ -1254,9 +1329,17 @@ class Engine:
                 for g in range(2, n_ctx):
                     cross(g)
                 self._join(forked)
-                self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["ao"], y, RQ, L.EPI_RESID, R=yn)
-                if RQ < RD:
+                rows_p = RQ
+                if RQ < RD and proj_b:
+                    w["ao"][RQ:RD].zero_()                     # groups without a context: proj(0) = its bias (below)
+                    rows_p = RD
+                self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["ao"], y, rows_p, L.EPI_RESID, R=yn)
+                if rows_p < RD:
                     y[RQ:RD].copy_(yn[RQ:RD])
+            elif proj_b:
+                # empty context, proj with a bias: attn @ v over an empty axis = 0, so the block adds proj(0) = bf16(bias) to every row
+                w["ao"][:RD].zero_()
+                self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["ao"], y, RD, L.EPI_RESID, R=yn)
             else:
                 # empty context: softmax over zero keys contributes nothing (attn @ v over an empty axis = 0) and the
                 # bias-free proj keeps it 0, so the cross-attention residual is the identity

@@ -60,6 +60,26 @@ def layernorm_bwd(dy, x, mean, rstd, w, dx_out, dw, dx_in=None, dx_bf16=None, dy
                                 _p(dx_bf16), _p(dw), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bwd")
 
 
+def layernorm_bias_fwd(x, w, b, y, mean, rstd, out_row=None, eps=1e-6, width=None):
+    """`layernorm_fwd` with the LayerNorm's bias: y = bf16(LN(x) * w + b)"""
+    _need_cuda(x)
+    rows, ld = x.shape
+    D = ld if width is None else width
+    check(L.load().ego_layernorm_bias_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), _p(out_row), rows, D, ld, eps, _stream()),
+          "ego_layernorm_bias_fwd")
+
+
+def layernorm_bias_bwd(dy, x, mean, rstd, w, dx_out, dw, db, dx_in=None, dx_bf16=None, dy_row=None, width=None):
+    """`layernorm_bwd` that also accumulates db += sum_rows dy"""
+    _need_cuda(x)
+    rows, ld = x.shape
+    D = ld if width is None else width
+    lib = L.load()
+    wk = _work(x.device, lib.ego_layernorm_bias_bwd_work_floats(rows, D))
+    check(lib.ego_layernorm_bias_bwd(_p(dy), _p(dy_row), _p(x), _p(mean), _p(rstd), _p(w), _p(dx_in), _p(dx_out),
+                                     _p(dx_bf16), _p(dw), _p(db), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bias_bwd")
+
+
 def _ptr_array(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
@@ -268,6 +288,18 @@ def gemm_nt_swiglu_bwd(dY, W2t, ab, dab, M, F, K, ldy=None, ldw=None):
 
 def swiglu_bwd(ab, dh, dab, rows, F):
     check(L.load().ego_swiglu_bwd(_p(ab), _p(dh), _p(dab), rows, F, _stream()), "ego_swiglu_bwd")
+
+
+def gelu_fwd(u, h, rows, F, ld_u=None, ld_h=None):
+    """h[rows, F] = bf16(gelu(u)) (erf form, fp32 math); ld_*: row pitches (default: the tensors' own)"""
+    check(L.load().ego_gelu_fwd(_p(u), _p(h), rows, F, u.stride(-2) if ld_u is None else ld_u, h.stride(-2) if ld_h is None else ld_h,
+                                _stream()), "ego_gelu_fwd")
+
+
+def gelu_bwd(u, dh, du, rows, F, ld_u=None, ld_dh=None, ld_du=None):
+    """du = bf16(dh * gelu'(u)) on the stored bf16 pre-activation"""
+    check(L.load().ego_gelu_bwd(_p(u), _p(dh), _p(du), rows, F, u.stride(-2) if ld_u is None else ld_u,
+                                dh.stride(-2) if ld_dh is None else ld_dh, du.stride(-2) if ld_du is None else ld_du, _stream()), "ego_gelu_bwd")
 
 
 def ce_fwd(logits, ld, V, targets, rng, max_rows, lse, nll):

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import hashlib
 import math
+from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -90,9 +91,10 @@ def _xavier(name, out_f, in_f, seed, fan_out=None):
     return uniform(name, (out_f, in_f), -a, a, seed)
 
 
-def _ln(name, dim, seed, sd):
+def _ln(name, dim, seed, sd, bias=False):
     sd[name + ".weight"] = normal(name + ".weight", (dim,), 0.1, seed, mean=1.0)
-    sd[name + ".bias"] = torch.zeros(dim)  # zero *buffer* in the reference (LayerNorm(bias=False))
+    # zero *buffer* in the reference's LayerNorm(bias=False); a parameter - drawn non-zero, so that a dead bias path shows - with bias
+    sd[name + ".bias"] = normal(name + ".bias", (dim,), 0.1, seed) if bias else torch.zeros(dim)
 
 
 def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[str, torch.Tensor]:
@@ -101,6 +103,12 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
 
     D, F = cfg.dim, cfg.mlp_hidden
     sd: Dict[str, torch.Tensor] = {}
+    gelu, nb = getattr(cfg, "mlp", "swiglu") == "gelu", bool(getattr(cfg, "norm_bias", False))
+    _ln = partial(globals()["_ln"], bias=nb)
+
+    def lin_bias(name, n, on):      # non-zero biases (std 0.05) of the GELU / biased family, under the reference's names
+        if on:
+            sd[name] = normal(name, (n,), 0.05, seed)
     for m in cfg.mods:
         e = f"encoder_embeddings.{m.name}"
         d = f"decoder_embeddings.{m.name}"
@@ -124,7 +132,12 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
         sd[f"{p}.attn.proj.weight"] = _xavier(f"{p}.attn.proj.weight", D, D, seed)
         sd[f"{p}.mlp.fc1.weight"] = _xavier(f"{p}.mlp.fc1.weight", F, D, seed)
         sd[f"{p}.mlp.fc2.weight"] = _xavier(f"{p}.mlp.fc2.weight", D, F, seed)
-        sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        if not gelu:
+            sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        lin_bias(f"{p}.attn.qkv.bias", 3 * D, cfg.qkv_bias)
+        lin_bias(f"{p}.attn.proj.bias", D, cfg.proj_bias)
+        lin_bias(f"{p}.mlp.fc1.bias", F, cfg.mlp_bias)
+        lin_bias(f"{p}.mlp.fc2.bias", D, cfg.mlp_bias)
     _ln("encoder_norm", D, seed, sd)
     sd["decoder_proj_context.weight"] = _xavier("decoder_proj_context.weight", D, D, seed)
     sd["decoder_proj_context.bias"] = normal("decoder_proj_context.bias", (D,), 0.02, seed)
@@ -139,7 +152,15 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
         sd[f"{p}.cross_attn.proj.weight"] = _xavier(f"{p}.cross_attn.proj.weight", D, D, seed)
         sd[f"{p}.mlp.fc1.weight"] = _xavier(f"{p}.mlp.fc1.weight", F, D, seed)
         sd[f"{p}.mlp.fc2.weight"] = _xavier(f"{p}.mlp.fc2.weight", D, F, seed)
-        sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        if not gelu:
+            sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        lin_bias(f"{p}.self_attn.qkv.bias", 3 * D, cfg.qkv_bias)
+        lin_bias(f"{p}.self_attn.proj.bias", D, cfg.proj_bias)
+        lin_bias(f"{p}.cross_attn.q.bias", D, cfg.qkv_bias)
+        lin_bias(f"{p}.cross_attn.kv.bias", 2 * D, cfg.qkv_bias)
+        lin_bias(f"{p}.cross_attn.proj.bias", D, cfg.proj_bias)
+        lin_bias(f"{p}.mlp.fc1.bias", F, cfg.mlp_bias)
+        lin_bias(f"{p}.mlp.fc2.bias", D, cfg.mlp_bias)
     _ln("decoder_norm", D, seed, sd)
     sd["mask_token"] = normal("mask_token", (1, 1, D), 0.02, seed)
     if getattr(cfg, "num_register_tokens", 0):

@@ -26,9 +26,10 @@ extern "C" {
  * ego_bias_grad and ego_embed_bwd a scratch buffer for their atomic-free reductions; 4: ego_layernorm_fwd / _bwd take the
  * row pitch `ld` beside the normalised width D; 5: ego_compact_desc grew `seg_bad`, ego_embed_bwd_desc `vocab`, ego_ce_bwd / ego_ce_fwd_bwd / ego_loss_finalize take loss weights; 6 (round 5): register tokens - ego_compact_desc grew `n_reg`,
  * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
- * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; loaders must refuse other
- * versions) */
-#define EGO_ABI_VERSION 9
+ * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; 10: the GELU / biased
+ * family - EGO_EPI_BIAS_BF16, new ego_gelu_fwd / ego_gelu_bwd, ego_layernorm_bias_fwd / ego_layernorm_bias_bwd, ego_bias_grad
+ * takes any width; loaders must refuse other versions) */
+#define EGO_ABI_VERSION 10
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -36,6 +37,7 @@ extern "C" {
 #define EGO_EPI_F32 1         /* C(f32)  = acc                                            */
 #define EGO_EPI_RESID 2       /* C(f32)  = R(f32) + bf16(acc)        residual add         */
 #define EGO_EPI_BIAS_RESID 3  /* C(f32)  = R(f32) + bf16(acc + bias) context projection   */
+#define EGO_EPI_BIAS_BF16 4   /* C(bf16) = bf16(acc + bias)          biased linear        */
 
 int ego_abi_version(void);
 /* Tile family the GEMM entries may pick (1 = by shape, 0 = 128x128 kernels only, 2 = 256x256 wherever legal); same
@@ -168,11 +170,27 @@ long ego_layernorm_bwd_work_floats(int rows, int D);
 int ego_layernorm_bwd(const void* dy_bf16, const int* dy_row, const float* x, const float* mean, const float* rstd,
                       const float* w, const float* dx_in, float* dx_out, void* dx_out_bf16, float* dw, float* work,
                       long work_floats, int rows, int D, long ld, hipStream_t stream);
+/* LayerNorm WITH its bias - `norm_layer=partial(nn.LayerNorm, eps=1e-6)` of the GELU registrations (egom2p_model.py:881-978;
+ * LayerNorm, egom2p_utils.py:118-133): y(bf16)[out_row[r]] = bf16(LN(x[r]) * w + b) in fp32.  The contract of
+ * ego_layernorm_fwd / ego_layernorm_bwd (out_row / dy_row, D <= ld, saved mean / rstd, dx_in accumulation, zero pad columns)
+ * plus b; the backward also gives db += sum_rows dy, reduced like dw: the workgroup's partial row in `work`
+ * (>= ego_layernorm_bias_bwd_work_floats(rows, D) floats) is [dw | db], summed in a fixed order - no float atomics, bitwise
+ * reproducible.  No e4m3 copy, no multi-layer form: the biased family calls these once per layer. */
+int ego_layernorm_bias_fwd(const float* x, const float* w, const float* b, void* y_bf16, float* mean, float* rstd,
+                           const int* out_row, int rows, int D, long ld, float eps, hipStream_t stream);
+long ego_layernorm_bias_bwd_work_floats(int rows, int D);
+int ego_layernorm_bias_bwd(const void* dy_bf16, const int* dy_row, const float* x, const float* mean, const float* rstd,
+                           const float* w, const float* dx_in, float* dx_out, void* dx_out_bf16, float* dw, float* db,
+                           float* work, long work_floats, int rows, int D, long ld, hipStream_t stream);
 
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 inputs, fp32 MFMA accumulate.  Replaces F.linear under
  * autocast(bf16) (egom2p_utils.py:141-169, 180-203, 215-242; decoder_embeddings.py:372-383, 489-500)
  * and its dgrad (B = W^T).  m_range: optional device int[2] = {row offset, row count}; then M is an
- * upper bound for the grid and A/C/R rows start at the offset. */
+ * upper bound for the grid and A/C/R rows start at the offset.
+ * EGO_EPI_BIAS_BF16: a linear with its bias under autocast(bf16) - qkv / q / kv with `qkv_bias`, fc1 with `mlp_bias`
+ * (Attention / CrossAttention, egom2p_utils.py:172-244; Mlp, :136-151): C(bf16) = bf16(acc + bias[n]), the bias (fp32, 16-byte
+ * aligned, N entries) in its bf16 image as with EGO_EPI_BIAS_RESID, ONE rounding after the sum; bias = NULL -> EGO_ERR_ARG.
+ * proj / fc2 with a bias take EGO_EPI_BIAS_RESID.  Epilogues 0-3 are served by the kernels they had. */
 int ego_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const float* R, long ldr,
                      const float* bias, const int* m_range, int M, int N, int K, int epi, hipStream_t stream);
 /* C[Ni,Nj] += P[M,Ni]^T . Q[M,Nj] (wgrad).  Output rows [0,split_row) go to C0 (first rows0 valid),
@@ -267,6 +285,13 @@ int ego_attn_bwd_hd(const void* Q, long q_bs, long q_rs, const void* K, long k_b
 /* SwiGLU gate on the fused fc1||fc3 output ab[rows, 2F] (GatedMlp, egom2p_utils.py:167-169). */
 int ego_swiglu_fwd(const void* ab, void* h, long rows, int F, hipStream_t stream);
 int ego_swiglu_bwd(const void* ab, const void* dh, void* dab, long rows, int F, hipStream_t stream);
+/* GELU in its exact erf form on the bf16 pre-activation u[rows, F] of the plain Mlp (`fc2(gelu(fc1 x))`, nn.GELU():
+ * egom2p_utils.py:136-151): h = bf16(u / 2 * (1 + erf(u / sqrt 2))) and, on the same stored u, the autograd
+ * du = bf16(dh * (Phi(u) + u phi(u))) - fp32 math.  ld_*: row pitches in elements (>= F); F % 8 == 0, pitches % 8 == 0 and
+ * 16-byte aligned tensors, else EGO_ERR_ARG.  NaN stays NaN, gelu(+inf) = +inf, gelu(-inf) = -0. */
+int ego_gelu_fwd(const void* u, void* h, long rows, int F, long ld_u, long ld_h, hipStream_t stream);
+int ego_gelu_bwd(const void* u, const void* dh, void* du, long rows, int F, long ld_u, long ld_dh, long ld_du,
+                 hipStream_t stream);
 /* fc1||fc3 and the gate in one launch: ab[M,2F] = X[M,K] @ W13[2F,K]^T and h = bf16(bf16(silu(a)) * b) (GatedMlp.forward,
  * egom2p_utils.py:167-169).  A tile of the GEMM is 128 columns of the a half and the matching 128 columns of the b half,
  * so the gate is formed in the epilogue; ab is still stored (the backward reads it) but never read back.  Bitwise the
@@ -391,7 +416,9 @@ int ego_maskgit_select(const int* tokens, const float* probs, const long* positi
 int ego_cast_weight(const float* W, int rows, int cols, long ld_src, void* Wb, long ld_w, void* Wt, long ld_t,
                     int rows_dst, hipStream_t stream);
 int ego_cast_f32_bf16(const float* src, void* dst, long n, hipStream_t stream);
-/* db += column sums of g (the bias gradient of decoder_proj_context, egom2p_model.py:157); same partial-row scheme. */
+/* db += column sums of g[rows, D] (the bias gradient of decoder_proj_context, egom2p_model.py:157, and of every linear of the
+ * biased family: qkv / q / kv / proj, egom2p_utils.py:172-244, fc1 / fc2, :136-151); same partial-row scheme.  D % 8 == 0, any
+ * width: more than 2048 columns are walked in chunks of 2048 (widths up to 2048: the launch, and the bits, of before). */
 long ego_bias_grad_work_floats(long rows, int D);
 int ego_bias_grad(const void* g_bf16, long rows, int D, float* db, float* work, long work_floats, hipStream_t stream);
 
