@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -67,6 +67,29 @@ def head_layout(H: int, HD: int, min_pad: int = 0) -> Tuple[int, int]:
 
 def _pad128(n: int) -> int:
     return (n + 127) // 128 * 128
+
+
+class _Rows(NamedTuple):
+    """One operand of an attention launch (q, k, v or a gradient of one): bf16 rows inside tensor `t`, the first one `off`
+    elements in, `rs` elements apart; a sample's rows follow the previous sample's."""
+    t: torch.Tensor
+    off: int
+    rs: int
+
+    def args(self, n):        # the kernels' operand triple: address, elements between two samples of n rows, between two rows
+        return self.t.data_ptr() + 2 * self.off, n * self.rs, self.rs
+
+
+# The key interval [ks, ke) a query row may attend to, as the kernels take it: (ks, ke, stride per sample, stride per row).
+def _keys_per_sample(zero_b, n_valid):
+    """one interval [0, n_valid) per SAMPLE (key padding): the uniform form lets the attention kernels walk one (batch, head) pair
+    per XCD (L2-resident K / V)"""
+    return zero_b, n_valid, 1, 0
+
+
+def _keys_per_row(ks, ke, M):
+    """one interval per query ROW of M-row samples (the decoder's block-diagonal / causal self-attention mask)"""
+    return ks, ke, M, 1
 
 
 class _Lin:
@@ -215,6 +238,16 @@ class Engine:
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
 
+    def _per_group(self, w, fn, n):
+        """fn(0) .. fn(n - 1): a generation pass's attention launches, one per group of samples.  Two groups with a second lane
+        (w["lse2"], _attn_infer): fn(1) goes out first, on the second stream, and runs beside fn(0)"""
+        beside = n == 2 and w.get("lse2") is not None
+        forked = self._fork(lambda: fn(1)) if beside else None
+        for g in range(n):
+            if not (beside and g == 1):
+                fn(g)
+        self._join(forked)
+
     def _ring_next(self):
         self._ring_i = (self._ring_i + 1) % len(self.ring_b)
         return self.ring_b[self._ring_i]
@@ -226,18 +259,16 @@ class Engine:
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)
 
-    def _ln_bwd(self, *a, **kw):
-        """ops.layernorm_bwd - an HBM-bound launch that leaves the MFMA pipes idle - with the weight-gradient GEMM that was held
-        back (an MFMA-bound launch with no consumer before the next bucket boundary) beside it on a second stream: the GEMM
-        starts when the LayerNorm does, and the main stream goes on only after both (two MFMA kernels never overlap: that was
-        measured 5 - 26 % slower)."""
-        db = kw.pop("db", None)            # the norm's bias gradient (norm_bias): the biased entry
-        if db is not None:
-            a = a[:7] + (db,) + a[7:]
-        ln_bwd = ops.layernorm_bwd if db is None else ops.layernorm_bias_bwd
+    def _ln_bwd(self, dy, x, wname, st, dx_out, **kw):
+        """The backward of `_ln(x, wname, y, st)` (kw: dx_in, dx_bf16; dw and, with norm_bias, db are accumulated) - an HBM-bound
+        launch that leaves the MFMA pipes idle - with the weight-gradient GEMM that was held back (an MFMA-bound launch with no
+        consumer before the next bucket boundary) beside it on a second stream: the GEMM starts when the LayerNorm does, and the
+        main stream goes on only after both (two MFMA kernels never overlap: measured 5 - 26 % slower)."""
+        a = (dy, x, st[0], st[1], self.p[wname], dx_out, self.g[wname])
+        kw.update(width=self.Dl, db=self.g.get(wname[:-len("weight")] + "bias"))
         run, self._pend = self._pend, None
         if run is None:
-            return ln_bwd(*a, **kw)
+            return ops.layernorm_bwd(*a, **kw)
         main = torch.cuda.current_stream()
         e0, e1 = self._pair_ev[self._pair_i], self._pair_ev[self._pair_i + 1]
         self._pair_i = (self._pair_i + 2) % len(self._pair_ev)
@@ -246,7 +277,7 @@ class Engine:
             self.pair_stream.wait_event(e0)
             run()
             e1.record(self.pair_stream)
-        ln_bwd(*a, **kw)
+        ops.layernorm_bwd(*a, **kw)
         main.wait_event(e1)
 
     # ------------------------------------------------------------------------------------ parameters
@@ -383,12 +414,10 @@ class Engine:
                 lin(f"decoder.{i}.{s}.weight")
             lin(f"decoder.{i}.mlp.fc1.weight") if self.gelu else self._fuse13(f"decoder.{i}")
         lin("decoder_proj_context.weight")
-        for m in self.mods:
-            key = (f"decoder_embeddings.{m.name}.token_emb.weight" if cfg.share_embedding
-                   else f"decoder_embeddings.{m.name}.to_logits.weight")
-            lin(key)
         self.logit_key = {m.name: (f"decoder_embeddings.{m.name}.token_emb.weight" if cfg.share_embedding
                                    else f"decoder_embeddings.{m.name}.to_logits.weight") for m in self.mods}
+        for key in self.logit_key.values():
+            lin(key)
 
     def _fuse13(self, prefix):
         """fc1 and fc3 are adjacent in the flat buffer: expose them as one [2Fp, D] linear."""
@@ -399,15 +428,14 @@ class Engine:
         self.lin[f"{prefix}.mlp.fc13"] = _Lin(f"{prefix}.mlp.fc13", w, g, self.dev, fp8=self.fp8_forward, fp8_bwd=self.fp8_backward)
 
     # reference key layout <-> engine storage ----------------------------------------------------
+    def _is_buffer_key(self, key: str) -> bool:
+        """reference keys without storage here: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)"""
+        return key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key)
+
     def _view_for_key(self, key: str) -> Optional[torch.Tensor]:
-        F, Fp = self.F, self.Fp
-        if key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key):
-            return None                                   # buffers: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)
-        k = key.replace("decoder_embeddings", "DE").replace("encoder_embeddings", "EE")
-        if k.startswith("DE") and k.endswith("mod_emb"):
-            key = key.replace("decoder_embeddings", "encoder_embeddings")      # shared Parameter
-        if key.endswith("to_logits.weight") and self.cfg.share_embedding:
-            key = key.replace("to_logits.weight", "token_emb.weight")          # tied
+        if self._is_buffer_key(key):
+            return None
+        key = self._canon_key(key)
         return self._logical(key, self.p[key])
 
     def _logical(self, key: str, t: torch.Tensor) -> torch.Tensor:
@@ -452,8 +480,8 @@ class Engine:
         `load_state_dict` reports them as unexpected / raises under strict=True)."""
         unexpected = []
         for key, val in sd.items():
-            if key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key):
-                continue                                  # buffers: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)
+            if self._is_buffer_key(key):
+                continue
             if self._canon_key(key) not in self.p:
                 unexpected.append(key)
                 continue
@@ -578,6 +606,17 @@ class Engine:
         self.weights_dirty = False
 
     # ------------------------------------------------------------------------------------ workspaces
+    def _compact_out(self, B, n_keep, train=False):
+        """the buffers one ops.compact call fills for B samples of n_keep kept rows (seg_bad: the training decoder's row groups)"""
+        i32 = dict(device=self.dev, dtype=I32)
+        out = {k: torch.empty(B, n_keep, device=self.dev, dtype=dt) for k, dt in (
+            ("ids_keep", torch.int64), ("pad", torch.uint8), ("mod_mask", torch.int16), ("slot", I32), ("local", I32), ("tok", I32),
+            ("ks", I32), ("ke", I32))}
+        out.update(n_valid=torch.zeros(B, **i32), seg=torch.empty(B, self.n_mods, 2, **i32), err=torch.zeros(1, **i32))
+        if train:
+            out["seg_bad"] = torch.zeros(B, **i32)
+        return out
+
     def _alloc_workspaces(self):
         B, N, M, D, A, Fp, H = self.Bmax, self.Ne, self.M, self.D, self.A, self.Fp, self.Hs      # N: encoder rows per sample (registers included)
         dev, cfg = self.dev, self.cfg
@@ -586,14 +625,7 @@ class Engine:
         def e(*shape, dt=BF16):
             return torch.empty(*shape, device=dev, dtype=dt)
 
-        def side(n_keep, n_rows):
-            return dict(ids_keep=e(B, n_keep, dt=torch.int64), pad=e(B, n_keep, dt=torch.uint8),
-                        mod_mask=e(B, n_keep, dt=torch.int16), slot=e(B, n_keep, dt=I32), local=e(B, n_keep, dt=I32),
-                        tok=e(B, n_keep, dt=I32), ks=e(B, n_keep, dt=I32), ke=e(B, n_keep, dt=I32),
-                        n_valid=e(B, dt=I32), seg=e(B, self.n_mods, 2, dt=I32), err=torch.zeros(1, device=dev, dtype=I32),
-                        seg_bad=torch.zeros(B, device=dev, dtype=I32))
-
-        self.ce, self.cd = side(N, RN), side(M, RM)
+        self.ce, self.cd = self._compact_out(B, N, train=True), self._compact_out(B, M, train=True)
         self.zero_b = torch.zeros(B, device=dev, dtype=I32)
         self.emb_e = e(RN, D, dt=F32)
         self.perm = e(RM, dt=I32)
@@ -662,19 +694,18 @@ class Engine:
         self.gscale = torch.ones(1, device=dev, dtype=F32)
 
     # ------------------------------------------------------------------------------------ small helpers
-    def _ln(self, x, wname, y, st, out_row=None):
-        """LayerNorm forward; with the fp8 forward on, the row also leaves as e4m3 (+ scale) for the GEMM that follows
-        (no separate quantisation pass for the LayerNorm-fed linears)."""
+    def _ln(self, x, wname, y, st, out_row=None, q8=True):
+        """LayerNorm forward (out_row: rows written permuted - decoder_norm); with the fp8 forward on, the row also leaves as
+        e4m3 (+ scale) for the GEMM that follows (no separate quantisation pass for the LayerNorm-fed linears; q8=False: the
+        consumer is no such linear)."""
         rows = x.shape[0]
-        if self.norm_bias:            # nn.LayerNorm with its bias: the biased entry, once per layer
-            ops.layernorm_bias_fwd(x, self.p[wname], self.p[wname[:-len("weight")] + "bias"], y, st[0], st[1], out_row=out_row,
-                                   eps=self.cfg.eps, width=self.Dl)
-        elif self.fp8_forward and out_row is None and self.D % 128 == 0 and self.D >= 256:
+        if q8 and self.fp8_forward and out_row is None and self.D % 128 == 0 and self.D >= 256:
             q = self._qbuf(rows, self.D)
             ops.layernorm_fwd(x, self.p[wname], y, st[0], st[1], eps=self.cfg.eps, q8=q, qscale=self.qs)
             self._q_of = (y.data_ptr(), rows, self.D)
-        else:
-            ops.layernorm_fwd(x, self.p[wname], y, st[0], st[1], out_row=out_row, eps=self.cfg.eps, width=self.Dl)
+        else:                         # (b: nn.LayerNorm's bias, a parameter with norm_bias only - never beside the fp8 forward)
+            ops.layernorm_fwd(x, self.p[wname], y, st[0], st[1], out_row=out_row, eps=self.cfg.eps, width=self.Dl,
+                              b=self.p.get(wname[:-len("weight")] + "bias"))
 
     def _qbuf(self, rows, K):
         if getattr(self, "q8", None) is None or self.q8.shape[0] < rows or self.q8.shape[1] < K:
@@ -716,9 +747,7 @@ class Engine:
             q = self._quant(xn, rows, l.in_f)
             ops.gemm_nt_swiglu_fwd_fp8(q, self.qs, l.w8, l.s8, ab, h, rows, self.Fp, l.in_f)
             return
-        # (fused launch from 3000 rows on: at 3414 rows - the paired decoder passes of a guided generation step - 29 us against 35 for
-        #  GEMM + gate pass; at 1707 rows the two launches win, 22 against 27: profiles/r05_gen_gemm_sweep_after.log)
-        if ops.swiglu_fwd_fusable(self.Fp, l.in_f) and rows >= 3000:
+        if ops.swiglu_fwd_fusable(self.Fp, l.in_f) and rows >= self.SWIGLU_FWD_FUSED_ROWS:
             ops.gemm_nt_swiglu_fwd(xn, l.wb, ab, h, rows, self.Fp, l.in_f, ldx=xn.shape[-1], ldw=l.in_f)
         else:
             self._lin_fwd(f"{pre}.mlp.fc13", xn, ab, rows)
@@ -758,16 +787,30 @@ class Engine:
                 self.side.wait_event(ev)
                 run()
 
-    def _attn(self, q_t, q_off, q_rs, kv_t, k_off, v_off, kv_rs, o_t, lse, ks, ke, r_bs, r_rs, B, Nq, Nk, o_lo=None, seg=None, seg_bad=None):
+    def _qkv_packed(self, t, r0=0):
+        """(q, k, v) of a [rows, 3A] qkv buffer (or its gradient), from row r0 on"""
         A = self.A
-        ops.attn_fwd(q_t.data_ptr() + 2 * q_off, Nq * q_rs, q_rs, kv_t.data_ptr() + 2 * k_off, Nk * kv_rs, kv_rs,
-                     kv_t.data_ptr() + 2 * v_off, Nk * kv_rs, kv_rs, o_t.data_ptr(), Nq * A, A, lse, ks, ke, r_bs, r_rs,
+        return _Rows(t, r0 * 3 * A, 3 * A), _Rows(t, r0 * 3 * A + A, 3 * A), _Rows(t, r0 * 3 * A + 2 * A, 3 * A)
+
+    def _q_kv(self, q_t, kv_t, r0=0, c0=0):
+        """(q, k, v) of cross-attention: q [rows, A] from row r0 on against kv [context rows, 2A] from context row c0 on"""
+        A = self.A
+        return _Rows(q_t, r0 * A, A), _Rows(kv_t, c0 * 2 * A, 2 * A), _Rows(kv_t, c0 * 2 * A + A, 2 * A)
+
+    def _attn(self, qkv, o_t, lse, mask, B, Nq, Nk, o_lo=None, seg=None, seg_bad=None):
+        """qkv: (q, k, v) `_Rows`; o_t [B * Nq, A] (o_lo: its bf16 rounding residual); mask: `_keys_per_sample` / `_keys_per_row`"""
+        q, k, v = qkv
+        ops.attn_fwd(*q.args(Nq), *k.args(Nk), *v.args(Nk), *_Rows(o_t, 0, self.A).args(Nq), lse, *mask,
                      B, self.Hs, Nq, Nk, self.scale, o_lo=None if o_lo is None else o_lo.data_ptr(), hd_pad=self.HDP,
                      seg=seg, seg_bad=seg_bad, hd=self.HD)
 
     # generation path: under-filled attention grids (1707 decoder rows x 12 heads = 168 workgroups on 256 CUs, each walking every
     # key tile serially: 26 - 47 us per launch) get their keys cut into runs (ego_attn_fwd_d64_split) until ~640 workgroups exist
     SPLIT_TARGET_WGS = 640
+    # fc1||fc3 + gate in one launch from this many rows on: at 3414 rows - the paired decoder passes of a guided generation step - 29 us
+    # against 35 for GEMM + gate pass; at 1707 rows the two launches win, 22 against 27: profiles/r05_gen_gemm_sweep_after.log
+    SWIGLU_FWD_FUSED_ROWS = 3000
+    SWIGLU_BWD_FUSED_ROWS = 4096        # fc2 dgrad + gate backward in one launch (_mlp_bwd) from this many rows on
 
     def _kv_splits(self, B, Nq, Nk):
         """Key runs per query tile of a generation-path attention launch (ego_attn_fwd_d64_split), from the measured table
@@ -790,21 +833,20 @@ class Engine:
             s = 1
         return max(1, min(s, ((Nk + 63) // 64) // 4))         # at least four 64-key tiles per run
 
-    def _attn_infer(self, w, q_t, q_off, q_rs, kv_t, k_off, v_off, kv_rs, o_t, ks, ke, B, Nq, Nk, lane=0):
-        """`_attn` of the generation passes: one interval per sample, no LSE consumer, split keys when the grid is small.
+    def _attn_infer(self, w, qkv, o_t, mask, B, Nq, Nk, lane=0):
+        """`_attn` of the generation passes: no LSE consumer, split keys when the grid is small.
         lane = 1: a launch that runs BESIDE another attention launch (_fork): its own split scratch and LSE rows"""
-        A = self.A
         sp = self._kv_splits(B, Nq, Nk)
         wkey, lkey = ("att_ws", "lse") if lane == 0 else ("att_ws2", "lse2")
         ws = w.get(wkey)
         if sp > 1 and ws is not None and ws.numel() < ops.attn_fwd_split_floats(B, self.Hs, Nq, sp) and not torch.cuda.is_current_stream_capturing():
             ws = w[wkey] = torch.empty(ops.attn_fwd_split_floats(B, self.Hs, Nq, sp) + 4096, device=self.dev, dtype=F32)
         if sp > 1 and ws is not None and ws.numel() >= ops.attn_fwd_split_floats(B, self.Hs, Nq, sp):
-            ops.attn_fwd_split(q_t.data_ptr() + 2 * q_off, Nq * q_rs, q_rs, kv_t.data_ptr() + 2 * k_off, Nk * kv_rs, kv_rs,
-                               kv_t.data_ptr() + 2 * v_off, Nk * kv_rs, kv_rs, o_t.data_ptr(), Nq * A, A, w[lkey], ks, ke, 1, 0,
+            q, k, v = qkv
+            ops.attn_fwd_split(*q.args(Nq), *k.args(Nk), *v.args(Nk), *_Rows(o_t, 0, self.A).args(Nq), w[lkey], *mask,
                                B, self.Hs, Nq, Nk, self.scale, sp, ws)
         else:
-            self._attn(q_t, q_off, q_rs, kv_t, k_off, v_off, kv_rs, o_t, w[lkey], ks, ke, 1, 0, B, Nq, Nk)
+            self._attn(qkv, o_t, w[lkey], mask, B, Nq, Nk)
 
     def _dec_groups(self):
         """Row groups of the decoder's block-diagonal self-attention mask for the attention kernels (head dim 64): the
@@ -818,14 +860,27 @@ class Engine:
         n = len(self.fmods)
         return dict(seg=self.cd["seg"].view(-1)[:self.B * n * 2].view(self.B, n, 2), seg_bad=self.cd["seg_bad"][:self.B])
 
-    def _attn_bwd(self, q_t, q_off, q_rs, kv_t, k_off, v_off, kv_rs, o_t, do_t, lse, dq_t, dkv_t, ks, ke, r_bs, r_rs, B, Nq, Nk,
-                  o_lo=None, seg=None, seg_bad=None):
-        A = self.A
-        ops.attn_bwd(q_t.data_ptr() + 2 * q_off, Nq * q_rs, q_rs, kv_t.data_ptr() + 2 * k_off, Nk * kv_rs, kv_rs,
-                     kv_t.data_ptr() + 2 * v_off, Nk * kv_rs, kv_rs, o_t.data_ptr(), Nq * A, A, do_t.data_ptr(), Nq * A, A,
-                     lse, self.delta, dq_t.data_ptr() + 2 * q_off, Nq * q_rs, q_rs, dkv_t.data_ptr() + 2 * k_off, Nk * kv_rs,
-                     kv_rs, dkv_t.data_ptr() + 2 * v_off, Nk * kv_rs, kv_rs, ks, ke, r_bs, r_rs, B, self.Hs, Nq, Nk, self.scale,
+    def _attn_bwd(self, qkv, o_t, do_t, lse, dqkv, mask, B, Nq, Nk, o_lo=None, seg=None, seg_bad=None):
+        """the backward of `_attn(qkv, o_t, lse, mask, ...)`: do_t laid out like o_t, dqkv = (dq, dk, dv) laid out like qkv"""
+        (q, k, v), (dq, dk, dv) = qkv, dqkv
+        ops.attn_bwd(*q.args(Nq), *k.args(Nk), *v.args(Nk), *_Rows(o_t, 0, self.A).args(Nq), *_Rows(do_t, 0, self.A).args(Nq),
+                     lse, self.delta, *dq.args(Nq), *dk.args(Nk), *dv.args(Nk), *mask, B, self.Hs, Nq, Nk, self.scale,
                      o_lo=None if o_lo is None else o_lo.data_ptr(), hd_pad=self.HDP, seg=seg, seg_bad=seg_bad, hd=self.HD)
+
+    # ---- the two sub-layers every block has (Block.forward egom2p_utils.py:356-359, DecoderBlock.forward :387-391): the training
+    # forward hands in each layer's saved buffers, the generation passes their shared ones
+    def _attn_sublayer(self, pre, name, x, out, rows, ln, st, qkv, ao, attn):
+        """out = x + proj(attention(qkv(norm1(x)))) over `rows` rows; attn(): the site's attention launch(es), qkv -> ao"""
+        self._ln(x[:rows], f"{pre}.norm1.weight", ln, st)
+        self._lin_fwd(f"{pre}.{name}.qkv.weight", ln, qkv, rows)
+        attn()
+        self._lin_fwd(f"{pre}.{name}.proj.weight", ao, out, rows, L.EPI_RESID, R=x)
+
+    def _mlp_sublayer(self, pre, x, out, rows, ln, st, ab, h):
+        """out = x + fc2(act(fc1(norm2(x)))) over `rows` rows"""
+        self._ln(x[:rows], f"{pre}.norm2.weight", ln, st)
+        self._mlp_gate_fwd(pre, ln, ab, h, rows)
+        self._lin_fwd(f"{pre}.mlp.fc2.weight", h, out, rows, L.EPI_RESID, R=x)
 
     # ------------------------------------------------------------------------------------ forward
     def forward(self, mod_dict: Dict[str, Dict[str, torch.Tensor]], dec_order: Optional[Sequence[str]] = None,
@@ -843,7 +898,7 @@ class Engine:
         self._loss_mode = ops.LOSS_MODES[loss_type]
         if self.weights_dirty:
             self.refresh_weights()
-        cfg, D, A, Fp, N, M = self.cfg, self.D, self.A, self.Fp, self.Ne, self.M      # N: encoder rows per sample (registers included)
+        cfg, D, N, M = self.cfg, self.D, self.Ne, self.M      # N: encoder rows per sample (registers included)
         # the modalities of this micro-batch: the configured ones present in mod_dict, in configuration order (the reference takes
         # whatever is there, egom2p_model.py:706-714); slots, loss rows and the loss mean run over these
         unknown = [k for k in mod_dict if k not in {m.name for m in self.mods}]
@@ -888,55 +943,40 @@ class Engine:
         ops.loss_perm(cd["seg"], self.canon, cd["slot"], cd["tok"], B, M, n_mods, self.perm, self.tgt_perm,
                       self.ranges, self.perm_base)
 
-        # ---- encoder (egom2p_model.py:496-499; Block.forward egom2p_utils.py:356-359)
+        # ---- encoder (egom2p_model.py:496-499)
+        enc_keys = _keys_per_sample(self.zero_b, ce["n_valid"])             # the encoder rows as keys: self- and cross-attention
         for i, w in enumerate(self.enc):
             pre = f"encoder.{i}"
             nxt = self.enc[i + 1]["x"] if i + 1 < cfg.encoder_depth else self.x_enc_out
-            self._ln(w["x"][:RN], f"{pre}.norm1.weight", w["ln1"], w["st1"])
-            self._lin_fwd(f"{pre}.attn.qkv.weight", w["ln1"], w["qkv"], RN)
-            # key-padding mask = one interval [0, n_valid) per SAMPLE (the per-row copies ce["ks"/"ke"] hold the same
-            # numbers): the uniform form lets the attention kernels walk one (batch, head) pair per XCD (L2-resident K / V)
-            self._attn(w["qkv"], 0, 3 * A, w["qkv"], A, 2 * A, 3 * A, w["ao"], w["lse"], self.zero_b, ce["n_valid"], 1, 0, B, N, N,
-                       o_lo=w["ao_lo"])
-            self._lin_fwd(f"{pre}.attn.proj.weight", w["ao"], w["xm"], RN, L.EPI_RESID, R=w["x"])
-            self._ln(w["xm"][:RN], f"{pre}.norm2.weight", w["ln2"], w["st2"])
-            self._mlp_gate_fwd(pre, w["ln2"], w["ab"], w["h"], RN)
-            self._lin_fwd(f"{pre}.mlp.fc2.weight", w["h"], nxt, RN, L.EPI_RESID, R=w["xm"])
+            # (key-padding mask: the per-row copies ce["ks"/"ke"] hold the same numbers as the per-sample interval)
+            self._attn_sublayer(pre, "attn", w["x"], w["xm"], RN, w["ln1"], w["st1"], w["qkv"], w["ao"],
+                                lambda: self._attn(self._qkv_packed(w["qkv"]), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]))
+            self._mlp_sublayer(pre, w["xm"], nxt, RN, w["ln2"], w["st2"], w["ab"], w["h"])
         self._ln(self.x_enc_out[:RN], "encoder_norm.weight", self.xe, self.st_en)
         # context = decoder_proj_context(x) + encoder_emb   (egom2p_model.py:722)
         self._lin_fwd("decoder_proj_context.weight", self.xe, self.ctx, RN, L.EPI_BIAS_RESID, R=self.emb_e,
                       bias=self.p["decoder_proj_context.bias"])
 
-        # ---- decoder (egom2p_model.py:520-523; DecoderBlock.forward egom2p_utils.py:387-391)
+        # ---- decoder (egom2p_model.py:520-523)
+        dec_keys, groups = _keys_per_row(cd["ks"], cd["ke"], M), self._dec_groups()
         if self.ctx_ln_fused:
             ops.layernorm_fwd_multi(self.ctx[:RN], [self.p[f"decoder.{i}.context_norm.weight"] for i in range(cfg.decoder_depth)],
                                     [w["cn"] for w in self.dec], self.st_ctx[0], self.st_ctx[1], eps=cfg.eps, width=self.Dl)
         for i, w in enumerate(self.dec):
             pre = f"decoder.{i}"
             nxt = self.dec[i + 1]["x"] if i + 1 < cfg.decoder_depth else self.y_out
-            self._ln(w["x"][:RM], f"{pre}.norm1.weight", w["ln1"], w["st1"])
-            self._lin_fwd(f"{pre}.self_attn.qkv.weight", w["ln1"], w["qkv"], RM)
-            self._attn(w["qkv"], 0, 3 * A, w["qkv"], A, 2 * A, 3 * A, w["ao"], w["lse"], cd["ks"], cd["ke"], M, 1, B, M, M,
-                       o_lo=w["ao_lo"], **self._dec_groups())
-            self._lin_fwd(f"{pre}.self_attn.proj.weight", w["ao"], w["x1"], RM, L.EPI_RESID, R=w["x"])
+            self._attn_sublayer(pre, "self_attn", w["x"], w["x1"], RM, w["ln1"], w["st1"], w["qkv"], w["ao"],
+                                lambda: self._attn(self._qkv_packed(w["qkv"]), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups))
             self._ln(w["x1"][:RM], f"{pre}.query_norm.weight", w["qn"], w["stq"])
             self._lin_fwd(f"{pre}.cross_attn.q.weight", w["qn"], w["q"], RM)
             if not self.ctx_ln_fused:
                 self._ln(self.ctx[:RN], f"{pre}.context_norm.weight", w["cn"], w["stc"])
             self._lin_fwd(f"{pre}.cross_attn.kv.weight", w["cn"], w["kv"], RN)
-            self._attn(w["q"], 0, A, w["kv"], 0, A, 2 * A, w["xo"], w["lse_x"], self.zero_b, ce["n_valid"], 1, 0, B, M, N,
-                       o_lo=w["xo_lo"])
+            self._attn(self._q_kv(w["q"], w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
             self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["xo"], w["x2"], RM, L.EPI_RESID, R=w["x1"])
-            self._ln(w["x2"][:RM], f"{pre}.norm2.weight", w["ln2"], w["st2"])
-            self._mlp_gate_fwd(pre, w["ln2"], w["ab"], w["h"], RM)
-            self._lin_fwd(f"{pre}.mlp.fc2.weight", w["h"], nxt, RM, L.EPI_RESID, R=w["x2"])
+            self._mlp_sublayer(pre, w["x2"], nxt, RM, w["ln2"], w["st2"], w["ab"], w["h"])
         # decoder_norm, rows written modality-grouped (the row order of y[decoder_mod_mask == id], :633)
-        if self.norm_bias:
-            ops.layernorm_bias_fwd(self.y_out[:RM], self.p["decoder_norm.weight"], self.p["decoder_norm.bias"], self.yn, self.st_dn[0],
-                                   self.st_dn[1], out_row=self.perm if group_rows else None, eps=cfg.eps, width=self.Dl)
-        else:
-            ops.layernorm_fwd(self.y_out[:RM], self.p["decoder_norm.weight"], self.yn, self.st_dn[0], self.st_dn[1],
-                              out_row=self.perm if group_rows else None, eps=cfg.eps, width=self.Dl)
+        self._ln(self.y_out[:RM], "decoder_norm.weight", self.yn, self.st_dn, out_row=self.perm if group_rows else None, q8=False)
         self._have_fwd = True
         if not need_loss:
             return None
@@ -974,7 +1014,7 @@ class Engine:
             # plain Mlp: dh = dY W2, du = dh * gelu'(u) on the stored bf16 pre-activation, then fc1 (their bias gradients: _lin_bwd)
             self._lin_bwd(f"{pre}.mlp.fc2.weight", dres_b, w["h"], dh, rows)
             ops.gelu_bwd(w["ab"], dh, dab, rows, Fp)
-        elif ops.swiglu_bwd_fusable(Fp, l2.out_f) and rows >= 4096:
+        elif ops.swiglu_bwd_fusable(Fp, l2.out_f) and rows >= self.SWIGLU_BWD_FUSED_ROWS:
             # fc2 dgrad and the gate backward in one launch (dh never reaches HBM), then the fc2 wgrad
             ops.gemm_nt_swiglu_bwd(dres_b, l2.wt, w["ab"], dab, rows, Fp, l2.out_f, ldy=dres_b.shape[-1], ldw=l2.out_f)
             self._wgrad(l2.g, dres_b, w["h"], l2.out_f, l2.in_f, rows, ldp=dres_b.shape[-1], ldq=w["h"].shape[-1])
@@ -983,21 +1023,17 @@ class Engine:
             ops.swiglu_bwd(w["ab"], dh, dab, rows, Fp)
         self._lin_bwd(f"{pre}.mlp.fc1.weight" if self.gelu else f"{pre}.mlp.fc13", dab, w["ln2"], dln, rows)
         nb = self._ring_next()
-        self._ln_bwd(dln, xin[:rows], w["st2"][0], w["st2"][1], self.p[f"{pre}.norm2.weight"], dres, self.g[f"{pre}.norm2.weight"],
-                          dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.norm2.bias"))
+        self._ln_bwd(dln, xin[:rows], f"{pre}.norm2.weight", w["st2"], dres, dx_in=dres, dx_bf16=nb)
         return nb
 
-    def _self_attn_bwd(self, pre, attn_name, w, dres, dres_b, rows, Nq, ks, ke, r_bs=None, r_rs=1, groups=None):
-        A, B = self.A, self.B
-        r_bs = Nq if r_bs is None else r_bs
+    def _self_attn_bwd(self, pre, attn_name, w, dres, dres_b, rows, Nq, mask, groups=None):
         dao, dqkv, dln = self.t_a, self.t_3d, self.t_d2
         self._lin_bwd(f"{pre}.{attn_name}.proj.weight", dres_b, w["ao"], dao, rows)
-        self._attn_bwd(w["qkv"], 0, 3 * A, w["qkv"], A, 2 * A, 3 * A, w["ao"], dao, w["lse"], dqkv, dqkv, ks, ke, r_bs, r_rs, B, Nq, Nq,
+        self._attn_bwd(self._qkv_packed(w["qkv"]), w["ao"], dao, w["lse"], self._qkv_packed(dqkv), mask, self.B, Nq, Nq,
                        o_lo=w["ao_lo"], **(groups or {}))
         self._lin_bwd(f"{pre}.{attn_name}.qkv.weight", dqkv, w["ln1"], dln, rows)
         nb = self._ring_next()
-        self._ln_bwd(dln, w["x"][:rows], w["st1"][0], w["st1"][1], self.p[f"{pre}.norm1.weight"], dres, self.g[f"{pre}.norm1.weight"],
-                          dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.norm1.bias"))
+        self._ln_bwd(dln, w["x"][:rows], f"{pre}.norm1.weight", w["st1"], dres, dx_in=dres, dx_bf16=nb)
         return nb
 
     def _set_gscale(self, gscale):
@@ -1011,7 +1047,7 @@ class Engine:
         `gscale` (float or 1-element device tensor: the upstream d loss).  `bucket_done(name, lo, hi)` is
         called (in launch order) as soon as every kernel writing G[lo:hi] has been enqueued."""
         assert self._have_fwd, "backward() needs a forward()"
-        cfg, D, A, N, M, B = self.cfg, self.D, self.A, self.Ne, self.M, self.B       # N: encoder rows per sample (registers included)
+        cfg, D, N, M, B = self.cfg, self.D, self.Ne, self.M, self.B       # N: encoder rows per sample (registers included)
         RN, RM = B * N, B * M
         mods, ce, cd = self.fmods, self.ce, self.cd           # the modalities of the forward (absent ones: no kernel writes their gradients)
         if getattr(self, "_ce_done", None):
@@ -1023,6 +1059,7 @@ class Engine:
         else:
             self._set_gscale(gscale)
         bmap = {n: (lo, hi) for n, lo, hi in self.buckets}
+        enc_keys = _keys_per_sample(self.zero_b, ce["n_valid"])             # the encoder rows as keys: self- and cross-attention
 
         def done(name):
             self._join_side()          # the bucket's weight gradients come from the side stream
@@ -1044,17 +1081,14 @@ class Engine:
         for m in reversed(self.mods):                          # (every bucket is handed over, an absent modality's with zeros)
             done(f"dec_table.{m.name}" if cfg.share_embedding else f"to_logits.{m.name}")
         dres, dres_b = self.dres, self._ring_next()
-        if self.norm_bias:
-            ops.layernorm_bias_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
-                                   self.g["decoder_norm.weight"], self.g["decoder_norm.bias"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm,
-                                   width=self.Dl)
-        else:
-            ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
-                              self.g["decoder_norm.weight"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm, width=self.Dl)
+        ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
+                          self.g["decoder_norm.weight"], dx_in=None, dx_bf16=dres_b, dy_row=self.perm, width=self.Dl,
+                          db=self.g.get("decoder_norm.bias"))
 
         # ---- decoder layers
         first_ctx = True
         fused = self.ctx_ln_fused
+        dec_keys, groups = _keys_per_row(cd["ks"], cd["ke"], M), self._dec_groups()
         if fused and self.dcn is None:
             self.dcn = [torch.empty(self.Bmax * N, D, device=self.dev, dtype=BF16) for _ in range(cfg.decoder_depth)]
         for i in reversed(range(cfg.decoder_depth)):
@@ -1063,21 +1097,17 @@ class Engine:
             # cross attention
             dxo, dq, dkv, dln = self.t_a, self.t_a2, self.t_2d, self.t_d
             self._lin_bwd(f"{pre}.cross_attn.proj.weight", dres_b, w["xo"], dxo, RM)
-            self._attn_bwd(w["q"], 0, A, w["kv"], 0, A, 2 * A, w["xo"], dxo, w["lse_x"], dq, dkv, self.zero_b, ce["n_valid"],
-                           1, 0, B, M, N, o_lo=w["xo_lo"])
+            self._attn_bwd(self._q_kv(w["q"], w["kv"]), w["xo"], dxo, w["lse_x"], self._q_kv(dq, dkv), enc_keys, B, M, N, o_lo=w["xo_lo"])
             self._lin_bwd(f"{pre}.cross_attn.q.weight", dq, w["qn"], dln, RM)
             nb = self._ring_next()
-            self._ln_bwd(dln, w["x1"][:RM], w["stq"][0], w["stq"][1], self.p[f"{pre}.query_norm.weight"], dres,
-                              self.g[f"{pre}.query_norm.weight"], dx_in=dres, dx_bf16=nb, width=self.Dl, db=self.g.get(f"{pre}.query_norm.bias"))
+            self._ln_bwd(dln, w["x1"][:RM], f"{pre}.query_norm.weight", w["stq"], dres, dx_in=dres, dx_bf16=nb)
             dres_b = nb
             dcn = self.dcn[i] if fused else self.t_d3    # not t_d2: dq is still being read by the q-projection wgrad on the side stream
             self._lin_bwd(f"{pre}.cross_attn.kv.weight", dkv, w["cn"], dcn, RN)
             if not fused:
-                self._ln_bwd(dcn, self.ctx[:RN], w["stc"][0], w["stc"][1], self.p[f"{pre}.context_norm.weight"], self.dctx,
-                                  self.g[f"{pre}.context_norm.weight"], dx_in=None if first_ctx else self.dctx, width=self.Dl,
-                                  db=self.g.get(f"{pre}.context_norm.bias"))
+                self._ln_bwd(dcn, self.ctx[:RN], f"{pre}.context_norm.weight", w["stc"], self.dctx, dx_in=None if first_ctx else self.dctx)
             first_ctx = False
-            dres_b = self._self_attn_bwd(pre, "self_attn", w, dres, dres_b, RM, M, cd["ks"], cd["ke"], groups=self._dec_groups())
+            dres_b = self._self_attn_bwd(pre, "self_attn", w, dres, dres_b, RM, M, dec_keys, groups=groups)
             done(pre)                 # (the layer's context_norm weight is not in this bucket: "ctx_norms")
         if cfg.decoder_depth == 0:
             self.dctx[:RN].zero_()
@@ -1105,15 +1135,14 @@ class Engine:
         dxe_n = self.t_d
         self._lin_bwd("decoder_proj_context.weight", self.dctx_b, self.xe, dxe_n, RN)
         dxe, dxe_b = self.dxe, self._ring_next()
-        self._ln_bwd(dxe_n, self.x_enc_out[:RN], self.st_en[0], self.st_en[1], self.p["encoder_norm.weight"], dxe,
-                          self.g["encoder_norm.weight"], dx_in=None, dx_bf16=dxe_b, width=self.Dl, db=self.g.get("encoder_norm.bias"))
+        self._ln_bwd(dxe_n, self.x_enc_out[:RN], "encoder_norm.weight", self.st_en, dxe, dx_in=None, dx_bf16=dxe_b)
         done("bridge")
 
         # ---- encoder layers
         for i in reversed(range(cfg.encoder_depth)):
             w, pre = self.enc[i], f"encoder.{i}"
             dxe_b = self._mlp_bwd(pre, w, dxe, dxe_b, RN, w["xm"])
-            dxe_b = self._self_attn_bwd(pre, "attn", w, dxe, dxe_b, RN, N, self.zero_b, ce["n_valid"], r_bs=1, r_rs=0)
+            dxe_b = self._self_attn_bwd(pre, "attn", w, dxe, dxe_b, RN, N, enc_keys)
             done(pre)
         # encoder input embeddings: token rows, mod_emb (emb is used twice: x = tok + emb and context += emb)
         ops.embed_bwd([self.g[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
@@ -1175,14 +1204,8 @@ class Engine:
         def e(*shape, dt=BF16):
             return torch.empty(*shape, device=dev, dtype=dt)
 
-        def side():
-            return dict(ids_keep=e(B, Nmax, dt=torch.int64), pad=e(B, Nmax, dt=torch.uint8), mod_mask=e(B, Nmax, dt=torch.int16),
-                        slot=e(B, Nmax, dt=I32), local=e(B, Nmax, dt=I32), tok=e(B, Nmax, dt=I32), ks=e(B, Nmax, dt=I32),
-                        ke=e(B, Nmax, dt=I32), n_valid=torch.zeros(B, device=dev, dtype=I32), seg=e(B, self.n_mods, 2, dt=I32),
-                        err=torch.zeros(1, device=dev, dtype=I32))
-
         w = dict(
-            groups=G, sides=[side() for _ in range(G)],
+            groups=G, sides=[self._compact_out(B, Nmax) for _ in range(G)],
             xa=e(RE, D, dt=F32), xb=e(RE, D, dt=F32), emb=e(RE, D, dt=F32), ctx=e(RC, D, dt=F32),
             ya=e(RD, D, dt=F32), yb=e(RD, D, dt=F32),
             ln=e(max(R, RC), D), qkv=e(R, 3 * A), ao=e(R, A), ab=e(R, self.Fab), h=e(R, Fp), q=e(RD, A), cn=e(RC, D),
@@ -1222,7 +1245,7 @@ class Engine:
         (the conditional and the unconditional inputs of a guided step); the groups' rows lie back to back, every row-wise
         launch (LayerNorm, GEMMs, gate) covers all of them - the unconditional pass's 1707 / 3414 rows alone leave most CUs
         idle - compaction, embedding and self-attention run per group (own row counts)."""
-        cfg, D, A = self.cfg, self.D, self.A
+        cfg, D = self.cfg, self.D
         parts = [p for p in parts if p[2] > 0]
         R = sum(B * n for _, _, n, _ in parts)
         x, xn = w["xa"], w["xb"]
@@ -1233,25 +1256,17 @@ class Engine:
             ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods], [self.pos[m.name] for m in mods],
                           [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, side["slot"], side["local"], side["tok"],
                           x[r0:], w["emb"][r0:], B * N, D, reg=self.p["register_tokens"] if self.R else None)
+
+        def enc_attn(gi):
+            side, _, N, r0 = parts[gi]
+            self._attn_infer(w, self._qkv_packed(w["qkv"], r0), w["ao"][r0:], _keys_per_sample(w["zero_b"], side["n_valid"]), B, N, N,
+                             lane=1 if (gi == 1 and w.get("lse2") is not None) else 0)
+
         for i in range(cfg.encoder_depth):
             pre = f"encoder.{i}"
-            self._ln(x[:R], f"{pre}.norm1.weight", w["ln"], w["st"])
-            self._lin_fwd(f"{pre}.attn.qkv.weight", w["ln"], w["qkv"], R)
-            def enc_attn(gi):
-                side, _, N, r0 = parts[gi]
-                self._attn_infer(w, w["qkv"], r0 * 3 * A, 3 * A, w["qkv"], r0 * 3 * A + A, r0 * 3 * A + 2 * A, 3 * A, w["ao"][r0:], w["zero_b"],
-                                 side["n_valid"], B, N, N, lane=1 if (gi == 1 and w.get("lse2") is not None) else 0)
-            # the second group's self-attention (the unconditional inputs: 324 workgroups at 3414 rows) goes out first, on the second
-            # stream, and runs beside the first group's launch
-            forked = self._fork(lambda: enc_attn(1)) if (len(parts) == 2 and w.get("lse2") is not None) else None
-            enc_attn(0)
-            if len(parts) == 2 and w.get("lse2") is None:
-                enc_attn(1)
-            self._join(forked)
-            self._lin_fwd(f"{pre}.attn.proj.weight", w["ao"], xn, R, L.EPI_RESID, R=x)
-            self._ln(xn[:R], f"{pre}.norm2.weight", w["ln"], w["st"])
-            self._mlp_gate_fwd(pre, w["ln"], w["ab"], w["h"], R)
-            self._lin_fwd(f"{pre}.mlp.fc2.weight", w["h"], x, R, L.EPI_RESID, R=xn)
+            # (the second group - the unconditional inputs: 324 workgroups at 3414 rows - beside the first group's launch)
+            self._attn_sublayer(pre, "attn", x, xn, R, w["ln"], w["st"], w["qkv"], w["ao"], lambda: self._per_group(w, enc_attn, len(parts)))
+            self._mlp_sublayer(pre, xn, x, R, w["ln"], w["st"], w["ab"], w["h"])
         self._ln(x[:R], "encoder_norm.weight", w["ln"], w["st"])
         self._lin_fwd("decoder_proj_context.weight", w["ln"], w["ctx"], R, L.EPI_BIAS_RESID, R=w["emb"],
                       bias=self.p["decoder_proj_context.bias"])
@@ -1260,7 +1275,7 @@ class Engine:
         """Decoder half of a generation pass over len(parts) groups of B samples that decode the SAME positions against
         different contexts (parts[g] = (side, N_g, first context row); groups with an empty context last).  Everything
         but the cross-attention itself is one launch for all groups.  Returns bf16 logits [groups * B * M, V]."""
-        cfg, D, A = self.cfg, self.D, self.A
+        cfg, D = self.cfg, self.D
         tm = {m.name: m for m in self.mods}[target]
         B, M = dec_pos.shape
         G = len(parts)
@@ -1277,6 +1292,7 @@ class Engine:
         ops.embed_fwd(None, [self.pos[tm.name]], [self.p[f"encoder_embeddings.{tm.name}.mod_emb"]], self.p["mask_token"],
                       w["dslot"], local, w["dtok"], y, None, RD, D)
         w["full_m"].fill_(M)
+        all_keys = _keys_per_sample(w["zero_b"], w["full_m"])       # decoder self-attention is unmasked (sa_mask=None)
         fused = self.ctx_ln_fused and w.get("cns") is not None and RC > 0
         kv_side, kv_evs = None, None
         if fused and w.get("kvs") is not None and RQ > 0:
@@ -1298,10 +1314,8 @@ class Engine:
                                     w["cns"], w["st"][0], w["st"][1], eps=cfg.eps, width=self.Dl)
         for i in range(cfg.decoder_depth):
             pre = f"decoder.{i}"
-            self._ln(y[:RD], f"{pre}.norm1.weight", w["ln"], w["st"])
-            self._lin_fwd(f"{pre}.self_attn.qkv.weight", w["ln"], w["qkv"], RD)
-            self._attn_infer(w, w["qkv"], 0, 3 * A, w["qkv"], A, 2 * A, 3 * A, w["ao"], w["zero_b"], w["full_m"], G * B, M, M)
-            self._lin_fwd(f"{pre}.self_attn.proj.weight", w["ao"], yn, RD, L.EPI_RESID, R=y)
+            self._attn_sublayer(pre, "self_attn", y, yn, RD, w["ln"], w["st"], w["qkv"], w["ao"],
+                                lambda: self._attn_infer(w, self._qkv_packed(w["qkv"]), w["ao"], all_keys, G * B, M, M))
             proj_b = self.lin[f"{pre}.cross_attn.proj.weight"].b is not None
             if RQ > 0:
                 self._ln(yn[:RQ], f"{pre}.query_norm.weight", w["ln"], w["st"])
@@ -1319,16 +1333,9 @@ class Engine:
 
                 def cross(g):
                     side, n, c0 = parts[g]
-                    self._attn_infer(w, w["q"], g * RM * A, A, kvb, c0 * 2 * A, c0 * 2 * A + A, 2 * A, w["ao"][g * RM:], w["zero_b"],
-                                     side["n_valid"], B, M, n, lane=1 if (g == 1 and w.get("lse2") is not None) else 0)
-                # the two halves of a guided step attend different contexts: the second half beside the first
-                forked = self._fork(lambda: cross(1)) if (n_ctx == 2 and w.get("lse2") is not None) else None
-                cross(0)
-                if n_ctx == 2 and w.get("lse2") is None:
-                    cross(1)
-                for g in range(2, n_ctx):
-                    cross(g)
-                self._join(forked)
+                    self._attn_infer(w, self._q_kv(w["q"], kvb, g * RM, c0), w["ao"][g * RM:], _keys_per_sample(w["zero_b"], side["n_valid"]),
+                                     B, M, n, lane=1 if (g == 1 and w.get("lse2") is not None) else 0)
+                self._per_group(w, cross, n_ctx)                # the two halves of a guided step attend different contexts
                 rows_p = RQ
                 if RQ < RD and proj_b:
                     w["ao"][RQ:RD].zero_()                     # groups without a context: proj(0) = its bias (below)
@@ -1344,9 +1351,7 @@ class Engine:
                 # empty context: softmax over zero keys contributes nothing (attn @ v over an empty axis = 0) and the
                 # bias-free proj keeps it 0, so the cross-attention residual is the identity
                 y, yn = yn, y
-            self._ln(y[:RD], f"{pre}.norm2.weight", w["ln"], w["st"])
-            self._mlp_gate_fwd(pre, w["ln"], w["ab"], w["h"], RD)
-            self._lin_fwd(f"{pre}.mlp.fc2.weight", w["h"], yn, RD, L.EPI_RESID, R=y)
+            self._mlp_sublayer(pre, y, yn, RD, w["ln"], w["st"], w["ab"], w["h"])
             y, yn = yn, y
         self._join(kv_side)                                  # (every kv event has been waited for; a capture wants the branch joined)
         self._ln(y[:RD], "decoder_norm.weight", w["ln"], w["st"])
@@ -1423,61 +1428,53 @@ class Engine:
         graphs[key] = g                                            # most recently used last
         return g
 
-    def infer_logits_graphed(self, enc_inputs, n_enc: int, target: str, dec_pos: torch.Tensor) -> torch.Tensor:
-        """`infer_logits` replayed from a captured hipGraph (BASELINE config 4: "hipGraph-captured decode").
-        One graph per pass shape (batch, modalities, N, M, target): inputs are copied into static buffers, the
-        ~300 kernel launches of a pass are replayed with one host call, the logits land in a static buffer
-        that stays valid until the next replay of the same graph."""
+    def _replay(self, key, sets, dec_pos, V, alloc, run):
+        """The graphed generation passes: static copies of the input sets (modality -> (ids, mask)) and of dec_pos, a captured
+        `run(ws, static sets, static dec_pos, out)` over them (`_graphed`, keyed by key(modality names)), then copy-in and replay.
+        Returns the static bf16 logits [len(sets) * B * M, V]: valid until the next replay of the same graph."""
         if self.weights_dirty:
             self.refresh_weights()
         B, M = dec_pos.shape
-        names = tuple(m.name for m in self.mods if m.name in enc_inputs)
-        V = {m.name: m for m in self.mods}[target].vocab_size
+        names = tuple(m.name for m in self.mods if m.name in sets[0])
 
         def make_state():
-            return {"ws": self._alloc_infer(B, max(int(n_enc) + self.R, 1), M, fresh=True),
-                    "ids": {n: enc_inputs[n][0].reshape(B, -1).to(self.dev, torch.int64).clone() for n in names},
-                    "mask": {n: enc_inputs[n][1].reshape(B, -1).to(self.dev, torch.bool).clone() for n in names},
-                    "pos": dec_pos.to(self.dev, I32).clone(),
-                    "out": torch.empty(B * M, V, device=self.dev, dtype=BF16)}
-
-        graph, st = self._graphed((B, names, int(n_enc), M, target), make_state,
-                                  lambda st: self.infer_logits({n: (st["ids"][n], st["mask"][n]) for n in names}, n_enc, target, st["pos"],
-                                                               out=st["out"], ws=st["ws"]))
-        for n in names:
-            st["ids"][n].copy_(enc_inputs[n][0].reshape(B, -1))
-            st["mask"][n].copy_(enc_inputs[n][1].reshape(B, -1))
-        st["pos"].copy_(dec_pos)
-        graph.replay()
-        return st["out"].view(B, M, V)
-
-    def infer_logits_cfg_graphed(self, enc_cond, n_cond: int, enc_uncond, n_uncond: int, target: str, dec_pos: torch.Tensor):
-        """`infer_logits_cfg` (both passes of a guided step, one decoder pass) replayed from a captured hipGraph"""
-        if self.weights_dirty:
-            self.refresh_weights()
-        B, M = dec_pos.shape
-        names = tuple(m.name for m in self.mods if m.name in enc_cond)
-        V = {m.name: m for m in self.mods}[target].vocab_size
-        sets = (enc_cond, enc_uncond)
-
-        def make_state():
-            return {"ws": self._alloc_infer(B, max(int(n_cond), int(n_uncond), 1) + self.R, M, fresh=True, groups=2),
+            return {"ws": alloc(),
                     "ids": [{n: e[n][0].reshape(B, -1).to(self.dev, torch.int64).clone() for n in names} for e in sets],
                     "mask": [{n: e[n][1].reshape(B, -1).to(self.dev, torch.bool).clone() for n in names} for e in sets],
                     "pos": dec_pos.to(self.dev, I32).clone(),
-                    "out": torch.empty(2 * B * M, V, device=self.dev, dtype=BF16)}
+                    "out": torch.empty(len(sets) * B * M, V, device=self.dev, dtype=BF16)}
 
-        graph, st = self._graphed(("cfg", B, names, int(n_cond), int(n_uncond), M, target), make_state,
-                                  lambda st: self.infer_logits_cfg({n: (st["ids"][0][n], st["mask"][0][n]) for n in names}, n_cond,
-                                                                   {n: (st["ids"][1][n], st["mask"][1][n]) for n in names}, n_uncond,
-                                                                   target, st["pos"], out=st["out"], ws=st["ws"]))
+        graph, st = self._graphed(key(names), make_state,
+                                  lambda st: run(st["ws"], [{n: (i[n], m[n]) for n in names} for i, m in zip(st["ids"], st["mask"])],
+                                                 st["pos"], st["out"]))
         for k, e in enumerate(sets):
             for n in names:
                 st["ids"][k][n].copy_(e[n][0].reshape(B, -1))
                 st["mask"][k][n].copy_(e[n][1].reshape(B, -1))
         st["pos"].copy_(dec_pos)
         graph.replay()
-        return st["out"][:B * M].view(B, M, V), st["out"][B * M:].view(B, M, V)
+        return st["out"]
+
+    def infer_logits_graphed(self, enc_inputs, n_enc: int, target: str, dec_pos: torch.Tensor) -> torch.Tensor:
+        """`infer_logits` replayed from a captured hipGraph (BASELINE config 4: "hipGraph-captured decode").
+        One graph per pass shape (batch, modalities, N, M, target): inputs are copied into static buffers, the
+        ~300 kernel launches of a pass are replayed with one host call, the logits land in a static buffer
+        that stays valid until the next replay of the same graph."""
+        B, M = dec_pos.shape
+        V = {m.name: m for m in self.mods}[target].vocab_size
+        out = self._replay(lambda names: (B, names, int(n_enc), M, target), [enc_inputs], dec_pos, V,
+                           lambda: self._alloc_infer(B, max(int(n_enc) + self.R, 1), M, fresh=True),
+                           lambda ws, sets, pos, out: self.infer_logits(sets[0], n_enc, target, pos, out=out, ws=ws))
+        return out.view(B, M, V)
+
+    def infer_logits_cfg_graphed(self, enc_cond, n_cond: int, enc_uncond, n_uncond: int, target: str, dec_pos: torch.Tensor):
+        """`infer_logits_cfg` (both passes of a guided step, one decoder pass) replayed from a captured hipGraph"""
+        B, M = dec_pos.shape
+        V = {m.name: m for m in self.mods}[target].vocab_size
+        out = self._replay(lambda names: ("cfg", B, names, int(n_cond), int(n_uncond), M, target), [enc_cond, enc_uncond], dec_pos, V,
+                           lambda: self._alloc_infer(B, max(int(n_cond), int(n_uncond), 1) + self.R, M, fresh=True, groups=2),
+                           lambda ws, sets, pos, out: self.infer_logits_cfg(sets[0], n_cond, sets[1], n_uncond, target, pos, out=out, ws=ws))
+        return out[:B * M].view(B, M, V), out[B * M:].view(B, M, V)
 
     @torch.no_grad()
     def forward_logits(self, mod_dict, dec_order=None) -> Dict[str, torch.Tensor]:

@@ -29,11 +29,18 @@ def _need_cuda(*ts):
 
 
 # ------------------------------------------------------------------------------------------
-def layernorm_fwd(x, w, y, mean, rstd, out_row=None, eps=1e-6, q8=None, qscale=None, width=None):
-    """width: the normalised width when the rows are stored padded (x.shape[1] is the pitch; pad columns of x are zero)"""
+def layernorm_fwd(x, w, y, mean, rstd, out_row=None, eps=1e-6, q8=None, qscale=None, width=None, b=None):
+    """width: the normalised width when the rows are stored padded (x.shape[1] is the pitch; pad columns of x are zero)
+    b (optional): nn.LayerNorm's bias, y = bf16(LN(x) * w + b) - the biased entry, which has no e4m3 output"""
     _need_cuda(x)
     rows, ld = x.shape
     D = ld if width is None else width
+    if b is not None:
+        if q8 is not None:
+            raise L.EgoHipError("the biased LayerNorm has no e4m3 output (b with q8)")
+        check(L.load().ego_layernorm_bias_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), _p(out_row), rows, D, ld, eps, _stream()),
+              "ego_layernorm_bias_fwd")
+        return
     check(L.load().ego_layernorm_fwd(_p(x), _p(w), _p(y), _p(mean), _p(rstd), _p(out_row), rows, D, ld, eps, _p(q8),
                                      0 if q8 is None else q8.stride(-2), _p(qscale), _stream()), "ego_layernorm_fwd")
 
@@ -50,34 +57,20 @@ def _work(device, n_floats):
     return buf
 
 
-def layernorm_bwd(dy, x, mean, rstd, w, dx_out, dw, dx_in=None, dx_bf16=None, dy_row=None, width=None):
+def layernorm_bwd(dy, x, mean, rstd, w, dx_out, dw, dx_in=None, dx_bf16=None, dy_row=None, width=None, db=None):
+    """db (optional): the gradient of nn.LayerNorm's bias, db += sum_rows dy - the biased entry"""
     _need_cuda(x)
     rows, ld = x.shape
     D = ld if width is None else width
     lib = L.load()
+    if db is not None:
+        wk = _work(x.device, lib.ego_layernorm_bias_bwd_work_floats(rows, D))
+        check(lib.ego_layernorm_bias_bwd(_p(dy), _p(dy_row), _p(x), _p(mean), _p(rstd), _p(w), _p(dx_in), _p(dx_out),
+                                         _p(dx_bf16), _p(dw), _p(db), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bias_bwd")
+        return
     wk = _work(x.device, lib.ego_layernorm_bwd_work_floats(rows, D))
     check(lib.ego_layernorm_bwd(_p(dy), _p(dy_row), _p(x), _p(mean), _p(rstd), _p(w), _p(dx_in), _p(dx_out),
                                 _p(dx_bf16), _p(dw), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bwd")
-
-
-def layernorm_bias_fwd(x, w, b, y, mean, rstd, out_row=None, eps=1e-6, width=None):
-    """`layernorm_fwd` with the LayerNorm's bias: y = bf16(LN(x) * w + b)"""
-    _need_cuda(x)
-    rows, ld = x.shape
-    D = ld if width is None else width
-    check(L.load().ego_layernorm_bias_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), _p(out_row), rows, D, ld, eps, _stream()),
-          "ego_layernorm_bias_fwd")
-
-
-def layernorm_bias_bwd(dy, x, mean, rstd, w, dx_out, dw, db, dx_in=None, dx_bf16=None, dy_row=None, width=None):
-    """`layernorm_bwd` that also accumulates db += sum_rows dy"""
-    _need_cuda(x)
-    rows, ld = x.shape
-    D = ld if width is None else width
-    lib = L.load()
-    wk = _work(x.device, lib.ego_layernorm_bias_bwd_work_floats(rows, D))
-    check(lib.ego_layernorm_bias_bwd(_p(dy), _p(dy_row), _p(x), _p(mean), _p(rstd), _p(w), _p(dx_in), _p(dx_out),
-                                     _p(dx_bf16), _p(dw), _p(db), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bias_bwd")
 
 
 def _ptr_array(ts):

@@ -95,15 +95,10 @@ class KernelTimer:
             p = _pairs(ks, ke, r_bs, r_rs, B, Nq, Nk)
             return 10.0 * hd_pad * Hh * p, 2.0 * B * Hh * hd_pad * ((5 if o_lo is not None else 4) * Nq + 4 * Nk)
 
-        def rowcost(bytes_per_row_elem):
-            def c(*a, **k):
-                return 0.0, 0.0
-            return c
-
-        def c_ln_fwd(x, w, y, mean, rstd, out_row=None, eps=1e-6, q8=None, qscale=None, width=None):
+        def c_ln_fwd(x, w, y, mean, rstd, out_row=None, eps=1e-6, q8=None, qscale=None, width=None, b=None):
             return 0.0, x.shape[0] * x.shape[1] * (7.0 if q8 is not None else 6.0)
 
-        def c_ln_bwd(dy, x, mean, rstd, w, dx_out, dw, dx_in=None, dx_bf16=None, dy_row=None, width=None):
+        def c_ln_bwd(dy, x, mean, rstd, w, dx_out, dw, dx_in=None, dx_bf16=None, dy_row=None, width=None, db=None):
             n = x.shape[0] * x.shape[1]
             return 0.0, n * (2.0 + 4.0 + 4.0 + (4.0 if dx_in is not None else 0.0) + (2.0 if dx_bf16 is not None else 0.0))
 

@@ -244,11 +244,11 @@ def test_layernorm_with_bias(rows, D, ld):
     for _ in range(2):
         y = torch.full((rows, ld), 9.0, device=DEV, dtype=BF16)
         mean, rstd = torch.empty(rows, device=DEV), torch.empty(rows, device=DEV)
-        ops.layernorm_bias_fwd(x, w, b, y, mean, rstd, out_row=perm, eps=1e-6, width=D)
+        ops.layernorm_fwd(x, w, y, mean, rstd, out_row=perm, eps=1e-6, width=D, b=b)
         dx = torch.full((rows, ld), 9.0, device=DEV)
         dxb = torch.full((rows, ld), 9.0, device=DEV, dtype=BF16)
         dw, db = torch.zeros(ld, device=DEV), torch.zeros(ld, device=DEV)
-        ops.layernorm_bias_bwd(dy, x, mean, rstd, w, dx, dw, db, dx_in=dx_in, dx_bf16=dxb, dy_row=perm, width=D)
+        ops.layernorm_bwd(dy, x, mean, rstd, w, dx, dw, dx_in=dx_in, dx_bf16=dxb, dy_row=perm, width=D, db=db)
         outs.append((y, mean, rstd, dx, dxb, dw, db))
     torch.cuda.synchronize()
     y, mean, rstd, dx, dxb, dw, db = outs[0]
@@ -267,7 +267,7 @@ def test_layernorm_with_bias(rows, D, ld):
         assert bool((y[~written].float() == 9.0).all())
     # accumulation: db adds to what is there, like dw
     dw2, db2 = torch.full((ld,), 2.0, device=DEV), torch.full((ld,), 3.0, device=DEV)
-    ops.layernorm_bias_bwd(dy, x, mean, rstd, w, torch.empty_like(dx), dw2, db2, dx_in=None, dy_row=perm, width=D)
+    ops.layernorm_bwd(dy, x, mean, rstd, w, torch.empty_like(dx), dw2, dx_in=None, dy_row=perm, width=D, db=db2)
     assert torch.equal(dw2[:D], 2.0 + dw[:D]) and torch.equal(db2[:D], 3.0 + db[:D])
     for a, c in zip(outs[0], outs[1]):
         assert torch.equal(a.view(torch.int16) if a.dtype == BF16 else a, c.view(torch.int16) if c.dtype == BF16 else c)

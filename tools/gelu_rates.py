@@ -29,7 +29,7 @@ for _ in range(reps):
     ops.swiglu_bwd(ab, dh, dab, rows, F)
     ops.layernorm_fwd(x, w, y, mean, rstd)
     ops.layernorm_bwd(dy, x, mean, rstd, w, dx, dw, dx_in=dx, dx_bf16=dxb)
-    ops.layernorm_bias_fwd(x, w, b, y, mean, rstd)
-    ops.layernorm_bias_bwd(dy, x, mean, rstd, w, dx, dw, db, dx_in=dx, dx_bf16=dxb)
+    ops.layernorm_fwd(x, w, y, mean, rstd, b=b)
+    ops.layernorm_bwd(dy, x, mean, rstd, w, dx, dw, dx_in=dx, dx_bf16=dxb, db=db)
 torch.cuda.synchronize()
 print("done")
