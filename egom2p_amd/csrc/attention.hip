@@ -1094,7 +1094,7 @@ extern "C" int ego_attn_bwd_d64_seg(const void* Q, long q_bs, long q_rs, const v
     a.stagger = g_attn_stagger;
     if (B == 0 || Nq == 0) return EGO_OK;
     if (!check(a) || !check_seg(a) || do_rs % 8 || do_bs % 8 || dq_rs % 8 || dk_rs % 8 || dv_rs % 8 || dq_bs % 8 || dk_bs % 8 || dv_bs % 8 ||
-        o_rs % 4 || o_bs % 4 || ((((uintptr_t)dQ) | ((uintptr_t)dK) | ((uintptr_t)dV)) & 15)) return EGO_ERR_ARG;              // 16-byte gradient rows
+        o_rs % 8 || o_bs % 8 || ((((uintptr_t)dQ) | ((uintptr_t)dK) | ((uintptr_t)dV)) & 15)) return EGO_ERR_ARG;              // 16-byte gradient rows
     if (Nq > DKV_MAX_QTILES * 64) return EGO_ERR_ARG;          // per-q-tile interval summaries live in LDS
     const int extra = a.seg ? a.n_seg + 1 : 0;
     // timing-only probe builds (tools/abl_attn.sh; never the product): ATT_ONLY 1 = dQ kernel only, 2 = dK / dV kernel only;
