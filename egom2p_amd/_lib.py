@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EGOM2P_HIP_LIB", os.path.join(_HERE, "libegom2p_hip.so"))   # override: kernel experiments
 MAX_MODS = 8
 
-ABI_VERSION = 10         # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
+ABI_VERSION = 11         # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
 EPI_BF16, EPI_F32, EPI_RESID, EPI_BIAS_RESID, EPI_BIAS_BF16 = 0, 1, 2, 3, 4
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
@@ -54,6 +54,11 @@ class EmbedBwdDesc(C.Structure):
     ]
 
 
+class HeadNormOp(C.Structure):
+    _fields_ = [("x", vp), ("x_bs", i64), ("x_rs", i64), ("y", vp), ("y_bs", i64), ("y_rs", i64),
+                ("w", vp), ("mean", vp), ("rstd", vp), ("dw", vp)]
+
+
 _SIGS = {
     "ego_abi_version": [],
     "ego_gemm_kernel_mode": [i32, i32],
@@ -79,6 +84,9 @@ _SIGS = {
     "ego_layernorm_fwd_multi": [vp, i32, vp, vp, vp, vp, i32, i32, i64, f32, vp],
     "ego_layernorm_bwd_multi_work_floats": [i32, i32, i32],
     "ego_layernorm_bwd_multi": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp],
+    "ego_headnorm_fwd": [C.POINTER(HeadNormOp), i32, i32, i32, i32, i32, f32, vp],
+    "ego_headnorm_bwd_work_floats": [i32, i32, i32, i32],
+    "ego_headnorm_bwd": [C.POINTER(HeadNormOp), i32, i32, i32, i32, i32, vp, i64, vp],
     "ego_gemm_nt_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp],
     "ego_gemm_tn_bf16": [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp],
     "ego_quant_fp8_rows": [vp, i64, i64, i32, vp, i64, vp, vp],

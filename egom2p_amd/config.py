@@ -64,6 +64,7 @@ class ModelCfg:
     proj_bias: bool = False            # bias of the attention output projections
     mlp_bias: bool = False             # bias of fc1 / fc2
     norm_bias: bool = False            # LayerNorm with its bias (nn.LayerNorm; egom2p_utils.py:118-133)
+    qk_norm: bool = False              # per-head LayerNorm(head_dim) of q and k in every attention site (NormAttention / NormCrossAttention, egom2p_utils.py:247-332)
 
     @property
     def head_dim(self) -> int:
@@ -110,6 +111,12 @@ MODEL_CFGS: Dict[str, ModelCfg] = {
     "ego_384_2e_2d_gelu": ModelCfg("ego_384_2e_2d_gelu", 384, 2, 2, 6, mlp="gelu", qkv_bias=True, proj_bias=True, mlp_bias=True, norm_bias=True),
     "ego_gen_384_2e_2d_gelu": ModelCfg("ego_gen_384_2e_2d_gelu", 384, 2, 2, 6, modalities=("tok_rgb", "tok_depth"), mlp="gelu",
                                        qkv_bias=True, proj_bias=True, mlp_bias=True, norm_bias=True),
+    # the QK-norm family (egom2p_*_swiglu_qknorm_nobias, egom2p_model.py:1122-1196: a bias-free LayerNorm(64, eps 1e-6) on every head's q
+    # and k) at the tiny variant's width and parity-test depth: tests/golden/b2_qknorm.npz, gen_rgb2depth_qknorm.npz; ego_b_qknorm is
+    # the registered base geometry at full depth (`bench.py --model ego_b_qknorm`)
+    "ego_384_2e_2d_qknorm": ModelCfg("ego_384_2e_2d_qknorm", 384, 2, 2, 6, qk_norm=True),
+    "ego_gen_384_2e_2d_qknorm": ModelCfg("ego_gen_384_2e_2d_qknorm", 384, 2, 2, 6, modalities=("tok_rgb", "tok_depth"), qk_norm=True),
+    "ego_b_qknorm": ModelCfg("ego_b_qknorm", 768, 12, 12, 12, qk_norm=True),
     "ego_L_1152": ModelCfg("ego_L_1152", 1152, 24, 24, 18),
     "ego_L_1152_2e_2d": ModelCfg("ego_L_1152_2e_2d", 1152, 2, 2, 18),       # ego-L width (BASELINE config 5) at parity-test depth
     # the REGISTERED ego-L geometry (egom2p_model.py:1080-1092: dim 1020, 15 heads of 68, F = 2720) at parity-test depth;

@@ -878,6 +878,155 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-head LayerNorm of q / k (the QK-norm family: NormAttention / NormCrossAttention, egom2p_utils.py:247-332 - `q_norm(q)`,
+// `k_norm(k)` with a bias-free LayerNorm(head_dim = 64, eps) after the qkv / q / kv projection).  The operand is addressed like an
+// attention operand: sample b, row r, head h starts at b * bs + r * rs + h * 64 elements, so q and k are normalised where they lie
+// inside the [rows, 3A] / [rows, A] / [rows, 2A] buffers; nothing outside the B * n * H slices of 64 is touched.
+// A slice is 128 B: 8 lanes x 16 B, eight consecutive slices (heads of one row lie back to back) per wave access = 1 KiB, fully
+// coalesced wherever 8 heads are contiguous.  The two row sums run over the 8 lanes of a slice on the VALU (three DPP steps).
+// blockIdx.y picks the operand (self-attention: q and k of one qkv buffer in one launch).
+// ---------------------------------------------------------------------------------------------
+struct HnOp { const bf16_t* x; long x_bs, x_rs; bf16_t* y; long y_bs, y_rs; const float* w; float* mean; float* rstd; };
+struct HnArgs { HnOp op[2]; int n, H, n_ops; unsigned S; float eps; float* dw_part; };
+
+__device__ __forceinline__ float sum8(float v) {      // the sum over an aligned group of 8 lanes, in every one of them
+    v += EGO_DPP_F(v, EGO_DPP_QUAD_X1);
+    v += EGO_DPP_F(v, EGO_DPP_QUAD_X2);
+    v += EGO_DPP_F(v, EGO_DPP_HALF_MIRROR);
+    return v;
+}
+__device__ __forceinline__ float max8(float v) {
+    v = fmaxf(v, EGO_DPP_F(v, EGO_DPP_QUAD_X1));
+    v = fmaxf(v, EGO_DPP_F(v, EGO_DPP_QUAD_X2));
+    v = fmaxf(v, EGO_DPP_F(v, EGO_DPP_HALF_MIRROR));
+    return v;
+}
+__device__ __forceinline__ long hn_off(unsigned s, int n, int H, long bs, long rs) {     // slice index (b, r, h) -> element offset
+    const unsigned row = s / (unsigned)H, h = s - row * (unsigned)H;
+    const unsigned b = row / (unsigned)n, r = row - b * (unsigned)n;
+    return (long)b * bs + (long)r * rs + (long)h * 64;
+}
+__device__ __forceinline__ void hn_unpack(const u32x4 raw, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { f[2 * e] = bf16_to_f32(raw[e] & 0xffff); f[2 * e + 1] = bf16_to_f32(raw[e] >> 16); }
+}
+
+constexpr int HN_FWD_PASSES = 4;      // a workgroup's 256 lanes cover 32 slices per pass: 128 slices per workgroup
+constexpr int HN_BWD_PASSES = 8;      // 256 slices per workgroup and partial weight-gradient row
+
+__global__ __launch_bounds__(256) void headnorm_fwd_kernel(HnArgs a) {
+#pragma clang fp contract(off)
+    const HnOp& o = a.op[blockIdx.y];
+    const int sub = threadIdx.x & 7, grp = threadIdx.x >> 3;
+    const f32x4 w0 = *(const f32x4*)(o.w + sub * 8), w1 = *(const f32x4*)(o.w + sub * 8 + 4);
+    const float ww[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+    u32x4 raw[HN_FWD_PASSES];
+    unsigned sl[HN_FWD_PASSES];
+    // every pass's load first (a slice past the end re-reads the last slice and is not stored)
+#pragma unroll
+    for (int p = 0; p < HN_FWD_PASSES; ++p) {
+        sl[p] = blockIdx.x * (32u * HN_FWD_PASSES) + p * 32u + grp;
+        raw[p] = *(const u32x4*)(o.x + hn_off(min(sl[p], a.S - 1), a.n, a.H, o.x_bs, o.x_rs) + sub * 8);
+    }
+#pragma unroll
+    for (int p = 0; p < HN_FWD_PASSES; ++p) {
+        float f[8];
+        hn_unpack(raw[p], f);
+        // bf16 reaches 3.4e38: the squares of a slice of such values leave fp32, so a slice whose largest magnitude is 2^59 or more is
+        // normalised as 2^-70 x (LayerNorm is scale-free up to eps, and a power of two changes no mantissa); every other slice: c = 1
+        float am = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(f[e]));
+        am = max8(am);
+        const float c = am >= 0x1p59f ? 0x1p-70f : 1.f, ic = am >= 0x1p59f ? 0x1p70f : 1.f;
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { f[e] *= c; s += f[e] * (1.f / 64.f); }
+        const float mean = sum8(s);
+        float q = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; q += d * d; }
+        // (the floor only matters where var + eps c^2 is 0: a constant slice of huge values, whose x - mean is exactly 0)
+        const float rstd = rsqrtf(fmaxf(sum8(q) * (1.f / 64.f) + a.eps * c * c, 1e-37f));
+        if (sl[p] >= a.S) continue;
+        if (sub == 0) { o.mean[sl[p]] = mean * ic; o.rstd[sl[p]] = rstd * c; }
+        float y[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = (f[e] - mean) * rstd * ww[e];
+        const u32x4 out = {pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]), pack_bf16x2(y[4], y[5]), pack_bf16x2(y[6], y[7])};
+        *(u32x4*)(o.y + hn_off(sl[p], a.n, a.H, o.y_bs, o.y_rs) + sub * 8) = out;
+    }
+}
+
+// Backward: o.y holds dy (bf16, as the attention backward leaves it in the dq / dk slot) and receives dx in place;
+// dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy w, xhat = (x - mean) rstd from the RAW x and the saved statistics;
+// dw partial row of the workgroup: [operand][64], its lanes' sums combined through LDS in a fixed order (colsum_kernel sums the
+// workgroups in order: no float atomics).
+__global__ __launch_bounds__(256) void headnorm_bwd_kernel(HnArgs a) {
+#pragma clang fp contract(off)
+    __shared__ float red[32][64 + 1];
+    const HnOp& o = a.op[blockIdx.y];
+    const int sub = threadIdx.x & 7, grp = threadIdx.x >> 3;
+    const f32x4 w0 = *(const f32x4*)(o.w + sub * 8), w1 = *(const f32x4*)(o.w + sub * 8 + 4);
+    const float ww[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+    float dwa[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dwa[e] = 0.f;
+#pragma unroll 1
+    for (int pp = 0; pp < HN_BWD_PASSES; pp += 2) {
+        if (blockIdx.x * (32u * HN_BWD_PASSES) + pp * 32u >= a.S) break;      // (uniform over the workgroup)
+        // two slices per lane in flight: both slices' loads before the first store (dy is overwritten in place)
+        u32x4 xr[2], dr[2];
+        float mu[2], rs[2];
+        unsigned sl[2];
+        long yo[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            sl[u] = blockIdx.x * (32u * HN_BWD_PASSES) + (pp + u) * 32u + grp;
+            const unsigned sc = min(sl[u], a.S - 1);
+            yo[u] = hn_off(sc, a.n, a.H, o.y_bs, o.y_rs) + sub * 8;
+            xr[u] = *(const u32x4*)(o.x + hn_off(sc, a.n, a.H, o.x_bs, o.x_rs) + sub * 8);
+            dr[u] = *(const u32x4*)(o.y + yo[u]);
+            mu[u] = o.mean[sc];
+            rs[u] = o.rstd[sc];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            float x[8], d[8];
+            hn_unpack(xr[u], x);
+            hn_unpack(dr[u], d);
+            const bool live = sl[u] < a.S;
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                x[e] = (x[e] - mu[u]) * rs[u];               // xhat
+                const float g = d[e] * ww[e];
+                dwa[e] += live ? d[e] * x[e] : 0.f;
+                d[e] = g;
+                s1 += g;
+                s2 += g * x[e];
+            }
+            const float c1 = sum8(s1) * (1.f / 64.f), c2 = sum8(s2) * (1.f / 64.f);
+            if (!live) continue;
+            float r[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) r[e] = rs[u] * (d[e] - c1 - x[e] * c2);
+            const u32x4 out = {pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3]), pack_bf16x2(r[4], r[5]), pack_bf16x2(r[6], r[7])};
+            *(u32x4*)(o.y + yo[u]) = out;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[grp][sub * 8 + e] = dwa[e];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float t = 0.f;
+#pragma unroll 8
+        for (int g = 0; g < 32; ++g) t += red[g][threadIdx.x];
+        a.dw_part[((long)blockIdx.x * a.n_ops + blockIdx.y) * 64 + threadIdx.x] = t;
+    }
+}
+
 inline int grid_for(long total, int cap = 4096) { return (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap); }
 
 }  // namespace
@@ -976,6 +1125,60 @@ extern "C" int ego_layernorm_bias_bwd(const void* dy, const int* dy_row, const f
     ColsumDst dst{};
     dst.p[0] = dw; dst.p[1] = db; dst.seg = D;          // partial rows are [dw | db]: column c goes to p[c / D][c % D]
     colsum_launch(work, nwg, 2 * D, dst, stream);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+// Per-head LayerNorm of q / k - `self.q_norm(q)`, `self.k_norm(k)` of NormAttention / NormCrossAttention
+// (egom2p/models/egom2p_utils.py:260-269, 304-316) - forward and backward: contract in egom2p_hip.h
+static bool hn_fill(HnArgs& a, const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, bool bwd) {
+    if (!ops || n_ops < 1 || n_ops > 2 || hd != 64 || B <= 0 || n <= 0 || H <= 0) return false;
+    const long S = (long)B * n * H;
+    if (S > 0x7fffffffL) return false;
+    for (int i = 0; i < n_ops; ++i) {
+        const ego_headnorm_op& p = ops[i];
+        if (!p.x || !p.y || !p.w || !p.mean || !p.rstd || (bwd && !p.dw)) return false;
+        // 16-byte accesses: aligned bases and strides; a row holds its H heads
+        if (((uintptr_t)p.x | (uintptr_t)p.y | (uintptr_t)p.w) & 15) return false;
+        if ((p.x_bs | p.x_rs | p.y_bs | p.y_rs) & 7) return false;
+        if (p.x_rs < (long)H * 64 || p.y_rs < (long)H * 64 || p.x_bs < 0 || p.y_bs < 0) return false;
+        a.op[i] = HnOp{(const bf16_t*)p.x, p.x_bs, p.x_rs, (bf16_t*)p.y, p.y_bs, p.y_rs, p.w, p.mean, p.rstd};
+    }
+    if (n_ops == 1) a.op[1] = a.op[0];
+    a.n = n; a.H = H; a.n_ops = n_ops; a.S = (unsigned)S;
+    return true;
+}
+
+extern "C" int ego_headnorm_fwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, float eps, hipStream_t stream) {
+    if (n_ops >= 1 && hd == 64 && (B == 0 || n == 0 || H == 0)) return EGO_OK;
+    HnArgs a{};
+    if (!hn_fill(a, ops, n_ops, B, n, H, hd, false)) return EGO_ERR_ARG;
+    a.eps = eps;
+    const unsigned per = 32u * HN_FWD_PASSES;
+    EGO_LAUNCH(headnorm_fwd_kernel, dim3((a.S + per - 1) / per, n_ops), dim3(256), 0, stream, a);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" long ego_headnorm_bwd_work_floats(int B, int n, int H, int n_ops) {
+    const long S = (long)(B > 0 ? B : 0) * (n > 0 ? n : 0) * (H > 0 ? H : 0), per = 32L * HN_BWD_PASSES;
+    return colsum_work_floats((S + per - 1) / per, 64 * (n_ops == 2 ? 2 : 1));
+}
+
+extern "C" int ego_headnorm_bwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, float* work, long work_floats,
+                                hipStream_t stream) {
+    if (n_ops >= 1 && hd == 64 && (B == 0 || n == 0 || H == 0)) return EGO_OK;
+    HnArgs a{};
+    if (!hn_fill(a, ops, n_ops, B, n, H, hd, true)) return EGO_ERR_ARG;
+    if (!work || work_floats < ego_headnorm_bwd_work_floats(B, n, H, n_ops)) return EGO_ERR_ARG;
+    a.dw_part = work;
+    const unsigned per = 32u * HN_BWD_PASSES, nwg = (a.S + per - 1) / per;
+    EGO_LAUNCH(headnorm_bwd_kernel, dim3(nwg, n_ops), dim3(256), 0, stream, a);
+    LAUNCH_CHECK();
+    ColsumDst dst{};
+    for (int i = 0; i < n_ops; ++i) dst.p[i] = ops[i].dw;          // partial rows are [operand 0 | operand 1]
+    dst.seg = 64;
+    colsum_launch(work, nwg, 64 * n_ops, dst, stream);
     LAUNCH_CHECK();
     return EGO_OK;
 }

@@ -164,6 +164,15 @@ class Engine:
             raise NotImplementedError("the GELU / biased family is built for unpadded storage (dim % 128 == 0, heads of 64)")
         if cfg.mlp_bias and not self.gelu:
             raise NotImplementedError("mlp_bias with the gated MLP (a bias on the fused fc1||fc3 launch) is not built: mlp_bias needs mlp='gelu'")
+        # the QK-norm family (egom2p_model.py:1122-1196; NormAttention / NormCrossAttention, egom2p_utils.py:247-332): a bias-free
+        # LayerNorm over every head's 64 q and k values, one [64] weight per site and operand (ego_headnorm_fwd / _bwd)
+        self.qk_norm = bool(getattr(cfg, "qk_norm", False))
+        if self.qk_norm and (self.padded or self.HD != 64):
+            raise NotImplementedError("qk_norm is built for unpadded storage (dim % 128 == 0, heads of 64): the head-norm kernels take heads of 64")
+        if self.qk_norm and (fp8_forward or fp8_backward):
+            raise NotImplementedError("qk_norm with the fp8 GEMMs (fp8_forward / fp8_backward) is not built: the QK-norm family runs in bf16 only")
+        if self.qk_norm and self.norm_bias:
+            raise NotImplementedError("qk_norm with norm_bias=True (the reference then gives the head norms a bias) is not built")
         self.Fab = self.Fp if self.gelu else 2 * self.Fp        # width of the saved MLP pre-activation rows: u, or a || b
         self.mods: List[Modality] = cfg.mods
         self.n_mods = len(self.mods)
@@ -301,6 +310,10 @@ class Engine:
             norms = ["norm1", "norm2"] if kind == "enc" else ["norm1", "query_norm", "norm2"]
             for n in norms:
                 norm(f"{prefix}.{n}")
+            if self.qk_norm:      # the head norms' weights (reference names), in the layer's no-decay run and its own bucket
+                for site in (("attn",) if kind == "enc" else ("self_attn", "cross_attn")):
+                    add(f"{prefix}.{site}.q_norm.weight", (self.HD,))
+                    add(f"{prefix}.{site}.k_norm.weight", (self.HD,))
             # the linears' biases (reference names) sit behind the norms: one no-decay run per layer, in the layer's own bucket
             lins = ([("attn.qkv", 3 * A, "qkv"), ("attn.proj", D, "proj")] if kind == "enc" else
                     [("self_attn.qkv", 3 * A, "qkv"), ("self_attn.proj", D, "proj"), ("cross_attn.q", A, "qkv"),
@@ -511,7 +524,7 @@ class Engine:
             if name.startswith(("encoder.", "decoder.", "encoder_norm", "decoder_norm", "decoder_proj_context")):
                 out[name] = ref(name)
                 if not self.norm_bias and (name.endswith("norm.weight") or ".norm" in name or "norm1" in name or "norm2" in name):
-                    out[name[:-len("weight")] + "bias"] = zeros
+                    out[name[:-len("weight")] + "bias"] = zeros if out[name].numel() == D else torch.zeros_like(out[name])   # (head norms: [64])
         out["mask_token"] = ref("mask_token").view(1, 1, D)
         if self.R:
             out["register_tokens"] = ref("register_tokens").view(1, self.R, D)
@@ -617,6 +630,20 @@ class Engine:
             out["seg_bad"] = torch.zeros(B, **i32)
         return out
 
+    def _hn_bufs(self, e, self_rows=0, q_rows=0, k_rows=0):
+        """qk_norm: the normalised q / k of a layer's sites and their statistics - qkn [rows, 3A] = (q^ | k^ | unused) of self-attention
+        with hst [(q mean, q rstd, k mean, k rstd), rows * H]; cross-attention: xqn [decoder rows, A], xkn [context rows, 2A] = (k^ |
+        unused), hstq / hstk [(mean, rstd), rows * H].  The raw q / k stay in qkv / q / kv: the backward normalises from them.
+        k^ keeps the pitch of the raw buffer because the attention kernels take K and V at ONE row stride (their LDS-DMA shares the
+        lane offsets of the two slices: `check` in attention.hip); the slot beside it is address space only - never written or read."""
+        if not self.qk_norm:
+            return {}
+        A, H = self.A, self.Hs
+        out = dict(qkn=e(self_rows, 3 * A), hst=e(4, self_rows * H, dt=F32))
+        if q_rows or k_rows:
+            out.update(xqn=e(q_rows, A), hstq=e(2, q_rows * H, dt=F32), xkn=e(k_rows, 2 * A), hstk=e(2, k_rows * H, dt=F32))
+        return out
+
     def _alloc_workspaces(self):
         B, N, M, D, A, Fp, H = self.Bmax, self.Ne, self.M, self.D, self.A, self.Fp, self.Hs      # N: encoder rows per sample (registers included)
         dev, cfg = self.dev, self.cfg
@@ -638,7 +665,7 @@ class Engine:
             return dict(x=e(RN, D, dt=F32), xm=e(RN, D, dt=F32), ln1=e(RN, D), qkv=e(RN, 3 * A), ao=e(RN, A),
                         ao_lo=e(RN, A) if self.attn_o_residual == "all" else None,
                         lse=e(B, H, N, dt=F32), st1=e(2, RN, dt=F32), ln2=e(RN, D), ab=e(RN, self.Fab), h=e(RN, Fp),
-                        st2=e(2, RN, dt=F32))
+                        st2=e(2, RN, dt=F32), **self._hn_bufs(e, self_rows=RN))
 
         def dec_layer():
             return dict(x=e(RM, D, dt=F32), x1=e(RM, D, dt=F32), x2=e(RM, D, dt=F32), ln1=e(RM, D), qkv=e(RM, 3 * A),
@@ -646,7 +673,8 @@ class Engine:
                         st1=e(2, RM, dt=F32), qn=e(RM, D), q=e(RM, A),
                         stq=e(2, RM, dt=F32), cn=e(RN, D), kv=e(RN, 2 * A), stc=e(2, RN, dt=F32), xo=e(RM, A),
                         xo_lo=e(RM, A) if self.attn_o_residual != "none" else None,
-                        lse_x=e(B, H, M, dt=F32), ln2=e(RM, D), ab=e(RM, self.Fab), h=e(RM, Fp), st2=e(2, RM, dt=F32))
+                        lse_x=e(B, H, M, dt=F32), ln2=e(RM, D), ab=e(RM, self.Fab), h=e(RM, Fp), st2=e(2, RM, dt=F32),
+                        **self._hn_bufs(e, self_rows=RM, q_rows=RM, k_rows=RN))
 
         self.enc = [enc_layer() for _ in range(cfg.encoder_depth)]
         self.dec = [dec_layer() for _ in range(cfg.decoder_depth)]
@@ -797,6 +825,46 @@ class Engine:
         A = self.A
         return _Rows(q_t, r0 * A, A), _Rows(kv_t, c0 * 2 * A, 2 * A), _Rows(kv_t, c0 * 2 * A + A, 2 * A)
 
+    # ---- qk_norm: q and k of an attention launch come from the normalised buffers, v from the raw one
+    def _qkv_site(self, w, r0=0):
+        """(q, k, v) of a self-attention site over the buffers w (a layer's, or a generation workspace), from row r0 on"""
+        q, k, v = self._qkv_packed(w["qkv"], r0)
+        if not self.qk_norm:
+            return q, k, v
+        A = self.A
+        return _Rows(w["qkn"], r0 * 3 * A, 3 * A), _Rows(w["qkn"], r0 * 3 * A + A, 3 * A), v
+
+    def _q_kv_site(self, w, kv_t, r0=0, c0=0):
+        """(q, k, v) of a cross-attention site: q rows from r0 on against the context rows from c0 on (kv_t: the raw [context rows, 2A])"""
+        q, k, v = self._q_kv(w["q"], kv_t, r0, c0)
+        if not self.qk_norm:
+            return q, k, v
+        return _Rows(w["xqn"], r0 * self.A, self.A), _Rows(w["xkn"], c0 * 2 * self.A, 2 * self.A), v
+
+    def _hn_self(self, pre, name, w, rows, grad=None):
+        """q_norm / k_norm of a self-attention site over `rows` contiguous rows, one launch: qkv -> qkn (+ statistics); grad = the
+        packed [rows, 3A] gradient: the backward, d q^ / d k^ -> d q / d k in place in its q and k slots, the weight gradients accumulated"""
+        A, H = self.A, self.Hs
+        q, k, _ = self._qkv_packed(w["qkv"])
+        sites = []
+        for j, (src, nm) in enumerate(((q, "q_norm"), (k, "k_norm"))):
+            dst = _Rows(w["qkn"] if grad is None else grad, j * A, 3 * A)
+            wn = f"{pre}.{name}.{nm}.weight"
+            sites.append((*src.args(rows), *dst.args(rows), self.p[wn], w["hst"][2 * j], w["hst"][2 * j + 1]) + (() if grad is None else (self.g[wn],)))
+        if grad is None:
+            ops.headnorm_fwd(sites, 1, rows, H, eps=self.cfg.eps)
+        else:
+            ops.headnorm_bwd(sites, 1, rows, H)
+
+    def _hn_one(self, wname, src, dst, st, rows, bwd=False):
+        """one operand's head norm over `rows` contiguous rows (cross-attention: q and k have different row counts); bwd: dst holds the
+        gradient, rewritten in place"""
+        site = (*src.args(rows), *dst.args(rows), self.p[wname], st[0], st[1])
+        if bwd:
+            ops.headnorm_bwd([site + (self.g[wname],)], 1, rows, self.Hs)
+        else:
+            ops.headnorm_fwd([site], 1, rows, self.Hs, eps=self.cfg.eps)
+
     def _attn(self, qkv, o_t, lse, mask, B, Nq, Nk, o_lo=None, seg=None, seg_bad=None):
         """qkv: (q, k, v) `_Rows`; o_t [B * Nq, A] (o_lo: its bf16 rounding residual); mask: `_keys_per_sample` / `_keys_per_row`"""
         q, k, v = qkv
@@ -869,10 +937,13 @@ class Engine:
 
     # ---- the two sub-layers every block has (Block.forward egom2p_utils.py:356-359, DecoderBlock.forward :387-391): the training
     # forward hands in each layer's saved buffers, the generation passes their shared ones
-    def _attn_sublayer(self, pre, name, x, out, rows, ln, st, qkv, ao, attn):
-        """out = x + proj(attention(qkv(norm1(x)))) over `rows` rows; attn(): the site's attention launch(es), qkv -> ao"""
+    def _attn_sublayer(self, pre, name, x, out, rows, ln, st, qkv, ao, attn, w=None):
+        """out = x + proj(attention(qkv(norm1(x)))) over `rows` rows; attn(): the site's attention launch(es), qkv -> ao
+        (w: the buffers holding qkv - with qk_norm also qkn / hst, filled here: attn() then reads `_qkv_site(w)`)"""
         self._ln(x[:rows], f"{pre}.norm1.weight", ln, st)
         self._lin_fwd(f"{pre}.{name}.qkv.weight", ln, qkv, rows)
+        if self.qk_norm:
+            self._hn_self(pre, name, w, rows)
         attn()
         self._lin_fwd(f"{pre}.{name}.proj.weight", ao, out, rows, L.EPI_RESID, R=x)
 
@@ -950,7 +1021,7 @@ class Engine:
             nxt = self.enc[i + 1]["x"] if i + 1 < cfg.encoder_depth else self.x_enc_out
             # (key-padding mask: the per-row copies ce["ks"/"ke"] hold the same numbers as the per-sample interval)
             self._attn_sublayer(pre, "attn", w["x"], w["xm"], RN, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_packed(w["qkv"]), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]))
+                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]), w=w)
             self._mlp_sublayer(pre, w["xm"], nxt, RN, w["ln2"], w["st2"], w["ab"], w["h"])
         self._ln(self.x_enc_out[:RN], "encoder_norm.weight", self.xe, self.st_en)
         # context = decoder_proj_context(x) + encoder_emb   (egom2p_model.py:722)
@@ -966,13 +1037,16 @@ class Engine:
             pre = f"decoder.{i}"
             nxt = self.dec[i + 1]["x"] if i + 1 < cfg.decoder_depth else self.y_out
             self._attn_sublayer(pre, "self_attn", w["x"], w["x1"], RM, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_packed(w["qkv"]), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups))
+                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups), w=w)
             self._ln(w["x1"][:RM], f"{pre}.query_norm.weight", w["qn"], w["stq"])
             self._lin_fwd(f"{pre}.cross_attn.q.weight", w["qn"], w["q"], RM)
             if not self.ctx_ln_fused:
                 self._ln(self.ctx[:RN], f"{pre}.context_norm.weight", w["cn"], w["stc"])
             self._lin_fwd(f"{pre}.cross_attn.kv.weight", w["cn"], w["kv"], RN)
-            self._attn(self._q_kv(w["q"], w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
+            if self.qk_norm:
+                self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RM)
+                self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RN)
+            self._attn(self._q_kv_site(w, w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
             self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["xo"], w["x2"], RM, L.EPI_RESID, R=w["x1"])
             self._mlp_sublayer(pre, w["x2"], nxt, RM, w["ln2"], w["st2"], w["ab"], w["h"])
         # decoder_norm, rows written modality-grouped (the row order of y[decoder_mod_mask == id], :633)
@@ -1029,8 +1103,10 @@ class Engine:
     def _self_attn_bwd(self, pre, attn_name, w, dres, dres_b, rows, Nq, mask, groups=None):
         dao, dqkv, dln = self.t_a, self.t_3d, self.t_d2
         self._lin_bwd(f"{pre}.{attn_name}.proj.weight", dres_b, w["ao"], dao, rows)
-        self._attn_bwd(self._qkv_packed(w["qkv"]), w["ao"], dao, w["lse"], self._qkv_packed(dqkv), mask, self.B, Nq, Nq,
+        self._attn_bwd(self._qkv_site(w), w["ao"], dao, w["lse"], self._qkv_packed(dqkv), mask, self.B, Nq, Nq,
                        o_lo=w["ao_lo"], **(groups or {}))
+        if self.qk_norm:          # d q^ / d k^ -> d q / d k in place (v's slot is not touched), q_norm / k_norm weight gradients
+            self._hn_self(pre, attn_name, w, rows, grad=dqkv)
         self._lin_bwd(f"{pre}.{attn_name}.qkv.weight", dqkv, w["ln1"], dln, rows)
         nb = self._ring_next()
         self._ln_bwd(dln, w["x"][:rows], f"{pre}.norm1.weight", w["st1"], dres, dx_in=dres, dx_bf16=nb)
@@ -1097,7 +1173,10 @@ class Engine:
             # cross attention
             dxo, dq, dkv, dln = self.t_a, self.t_a2, self.t_2d, self.t_d
             self._lin_bwd(f"{pre}.cross_attn.proj.weight", dres_b, w["xo"], dxo, RM)
-            self._attn_bwd(self._q_kv(w["q"], w["kv"]), w["xo"], dxo, w["lse_x"], self._q_kv(dq, dkv), enc_keys, B, M, N, o_lo=w["xo_lo"])
+            self._attn_bwd(self._q_kv_site(w, w["kv"]), w["xo"], dxo, w["lse_x"], self._q_kv(dq, dkv), enc_keys, B, M, N, o_lo=w["xo_lo"])
+            if self.qk_norm:
+                self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(dq, 0, self.A), w["hstq"], RM, bwd=True)
+                self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(dkv, 0, 2 * self.A), w["hstk"], RN, bwd=True)
             self._lin_bwd(f"{pre}.cross_attn.q.weight", dq, w["qn"], dln, RM)
             nb = self._ring_next()
             self._ln_bwd(dln, w["x1"][:RM], f"{pre}.query_norm.weight", w["stq"], dres, dx_in=dres, dx_bf16=nb)
@@ -1214,6 +1293,7 @@ class Engine:
             dslot=torch.zeros(RD, device=dev, dtype=I32), dtok=torch.zeros(RD, device=dev, dtype=I32),
         )
         w["side"] = w["sides"][0]
+        w.update(self._hn_bufs(e, self_rows=R, q_rows=RD, k_rows=RC))      # qk_norm: normalised q / k of the pass's sites
         # every decoder layer's context_norm output from one pass over the context (ego_layernorm_fwd_multi)
         w["cns"] = [e(RC, D) for _ in range(self.cfg.decoder_depth)] if self.ctx_ln_fused else None
         # scratch of the split-key attention launches: splits x B x H x ceil(Nq / 128) <= SPLIT_TARGET_WGS bounds it
@@ -1259,13 +1339,13 @@ class Engine:
 
         def enc_attn(gi):
             side, _, N, r0 = parts[gi]
-            self._attn_infer(w, self._qkv_packed(w["qkv"], r0), w["ao"][r0:], _keys_per_sample(w["zero_b"], side["n_valid"]), B, N, N,
+            self._attn_infer(w, self._qkv_site(w, r0), w["ao"][r0:], _keys_per_sample(w["zero_b"], side["n_valid"]), B, N, N,
                              lane=1 if (gi == 1 and w.get("lse2") is not None) else 0)
 
         for i in range(cfg.encoder_depth):
             pre = f"encoder.{i}"
             # (the second group - the unconditional inputs: 324 workgroups at 3414 rows - beside the first group's launch)
-            self._attn_sublayer(pre, "attn", x, xn, R, w["ln"], w["st"], w["qkv"], w["ao"], lambda: self._per_group(w, enc_attn, len(parts)))
+            self._attn_sublayer(pre, "attn", x, xn, R, w["ln"], w["st"], w["qkv"], w["ao"], lambda: self._per_group(w, enc_attn, len(parts)), w=w)
             self._mlp_sublayer(pre, xn, x, R, w["ln"], w["st"], w["ab"], w["h"])
         self._ln(x[:R], "encoder_norm.weight", w["ln"], w["st"])
         self._lin_fwd("decoder_proj_context.weight", w["ln"], w["ctx"], R, L.EPI_BIAS_RESID, R=w["emb"],
@@ -1315,7 +1395,7 @@ class Engine:
         for i in range(cfg.decoder_depth):
             pre = f"decoder.{i}"
             self._attn_sublayer(pre, "self_attn", y, yn, RD, w["ln"], w["st"], w["qkv"], w["ao"],
-                                lambda: self._attn_infer(w, self._qkv_packed(w["qkv"]), w["ao"], all_keys, G * B, M, M))
+                                lambda: self._attn_infer(w, self._qkv_site(w), w["ao"], all_keys, G * B, M, M), w=w)
             proj_b = self.lin[f"{pre}.cross_attn.proj.weight"].b is not None
             if RQ > 0:
                 self._ln(yn[:RQ], f"{pre}.query_norm.weight", w["ln"], w["st"])
@@ -1331,9 +1411,13 @@ class Engine:
                         self._ln(w["ctx"][:RC], f"{pre}.context_norm.weight", cn, w["st"])
                     self._lin_fwd(f"{pre}.cross_attn.kv.weight", cn, kvb, RC)
 
+                if self.qk_norm:
+                    self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RQ)
+                    self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(kvb, 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RC)
+
                 def cross(g):
                     side, n, c0 = parts[g]
-                    self._attn_infer(w, self._q_kv(w["q"], kvb, g * RM, c0), w["ao"][g * RM:], _keys_per_sample(w["zero_b"], side["n_valid"]),
+                    self._attn_infer(w, self._q_kv_site(w, kvb, g * RM, c0), w["ao"][g * RM:], _keys_per_sample(w["zero_b"], side["n_valid"]),
                                      B, M, n, lane=1 if (g == 1 and w.get("lse2") is not None) else 0)
                 self._per_group(w, cross, n_ctx)                # the two halves of a guided step attend different contexts
                 rows_p = RQ

@@ -97,6 +97,31 @@ def layernorm_bwd_multi(dys, x, mean, rstd, ws, dx_out, dws, dx_in=None, dx_bf16
                                       _p(dx_out), _p(dx_bf16), _p(wk), wk.numel(), rows, D, ld, _stream()), "ego_layernorm_bwd_multi")
 
 
+def _headnorm_ops(sites, bwd):
+    arr = (L.HeadNormOp * len(sites))()
+    for i, s in enumerate(sites):
+        x, x_bs, x_rs, y, y_bs, y_rs, w, mean, rstd = s[:9]
+        _need_cuda(w, mean, rstd)
+        arr[i] = L.HeadNormOp(x, x_bs, x_rs, y, y_bs, y_rs, _p(w), _p(mean), _p(rstd), _p(s[9]) if bwd else None)
+    return arr
+
+
+def headnorm_fwd(sites, B, n, H, eps=1e-6, hd=64):
+    """Per-head LayerNorm of q / k (the QK-norm family).  sites: one operand, or two of the same (B, n, H) - q and k of one qkv buffer -
+    each (x, x_bs, x_rs, y, y_bs, y_rs, w, mean, rstd): source and destination as attention operand triples (address, elements between
+    samples, between rows: `_Rows.args`), w [64] fp32, mean / rstd [B * n * H] fp32 (written).  y = bf16(LN(x) * w) per 64-wide head."""
+    check(L.load().ego_headnorm_fwd(_headnorm_ops(sites, False), len(sites), B, n, H, hd, eps, _stream()), "ego_headnorm_fwd")
+
+
+def headnorm_bwd(sites, B, n, H, hd=64):
+    """The backward of `headnorm_fwd`: sites as there plus dw [64] (accumulated) - x the RAW operand, y the gradient: d y in, d x out in
+    place, mean / rstd the forward's statistics."""
+    lib = L.load()
+    dev = sites[0][6].device
+    wk = _work(dev, lib.ego_headnorm_bwd_work_floats(B, n, H, len(sites)))
+    check(lib.ego_headnorm_bwd(_headnorm_ops(sites, True), len(sites), B, n, H, hd, _p(wk), wk.numel(), _stream()), "ego_headnorm_bwd")
+
+
 def gemm_nt(A, B, C_out, M, N, K, epi=L.EPI_BF16, R=None, bias=None, m_range=None, lda=None, ldb=None, ldc=None, ldr=None):
     """C[M,N] = A[M,K] @ B[N,K]^T (+ epilogue)."""
     _need_cuda(A)

@@ -106,6 +106,11 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
     gelu, nb = getattr(cfg, "mlp", "swiglu") == "gelu", bool(getattr(cfg, "norm_bias", False))
     _ln = partial(globals()["_ln"], bias=nb)
 
+    def head_norms(site):           # NormAttention / NormCrossAttention (egom2p_utils.py:247-332): q_norm, k_norm over one head
+        if getattr(cfg, "qk_norm", False):
+            _ln(f"{site}.q_norm", cfg.head_dim, seed, sd)
+            _ln(f"{site}.k_norm", cfg.head_dim, seed, sd)
+
     def lin_bias(name, n, on):      # non-zero biases (std 0.05) of the GELU / biased family, under the reference's names
         if on:
             sd[name] = normal(name, (n,), 0.05, seed)
@@ -134,6 +139,7 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
         sd[f"{p}.mlp.fc2.weight"] = _xavier(f"{p}.mlp.fc2.weight", D, F, seed)
         if not gelu:
             sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        head_norms(f"{p}.attn")
         lin_bias(f"{p}.attn.qkv.bias", 3 * D, cfg.qkv_bias)
         lin_bias(f"{p}.attn.proj.bias", D, cfg.proj_bias)
         lin_bias(f"{p}.mlp.fc1.bias", F, cfg.mlp_bias)
@@ -154,6 +160,8 @@ def build_state_dict(cfg: ModelCfg, seed: int = 0, posemb: bool = True) -> Dict[
         sd[f"{p}.mlp.fc2.weight"] = _xavier(f"{p}.mlp.fc2.weight", D, F, seed)
         if not gelu:
             sd[f"{p}.mlp.fc3.weight"] = _xavier(f"{p}.mlp.fc3.weight", F, D, seed)
+        head_norms(f"{p}.self_attn")
+        head_norms(f"{p}.cross_attn")
         lin_bias(f"{p}.self_attn.qkv.bias", 3 * D, cfg.qkv_bias)
         lin_bias(f"{p}.self_attn.proj.bias", D, cfg.proj_bias)
         lin_bias(f"{p}.cross_attn.q.bias", D, cfg.qkv_bias)

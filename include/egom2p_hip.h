@@ -28,8 +28,8 @@ extern "C" {
  * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
  * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; 10: the GELU / biased
  * family - EGO_EPI_BIAS_BF16, new ego_gelu_fwd / ego_gelu_bwd, ego_layernorm_bias_fwd / ego_layernorm_bias_bwd, ego_bias_grad
- * takes any width; loaders must refuse other versions) */
-#define EGO_ABI_VERSION 10
+ * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; loaders must refuse other versions) */
+#define EGO_ABI_VERSION 11
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -182,6 +182,32 @@ long ego_layernorm_bias_bwd_work_floats(int rows, int D);
 int ego_layernorm_bias_bwd(const void* dy_bf16, const int* dy_row, const float* x, const float* mean, const float* rstd,
                            const float* w, const float* dx_in, float* dx_out, void* dx_out_bf16, float* dw, float* db,
                            float* work, long work_floats, int rows, int D, long ld, hipStream_t stream);
+
+/* Per-head LayerNorm of q and k - the QK-norm family: `q = self.q_norm(q)`, `k = self.k_norm(k)` of NormAttention
+ * (egom2p/models/egom2p_utils.py:247-286, its lines 260-261 and 268-269) and NormCrossAttention (:289-332, its lines 304-305 and
+ * 315-316), norm_layer(head_dim) = the bias-free LayerNorm of :118-133 over ONE head's 64 values, its weight [64] shared by all heads.
+ * One operand = one of q / k of one site, addressed like an attention operand (ego_attn_fwd_d64): element 0 of sample b, row r,
+ * head h lies at x + b * x_bs + r * x_rs + h * 64 (strides in elements) for b < B, r < n, h < H - q and k are normalised where they lie
+ * inside the [rows, 3A] qkv, [rows, A] q and [context rows, 2A] kv buffers.  Forward: y = bf16(LN_fp32(x) * w) to the same slice
+ * of a separate destination (the raw x stays: the backward reads it), mean[s] / rstd[s] in fp32 for slice s = (b * n + r) * H + h.
+ * Backward (replaces the autograd of those lines): y holds d y (bf16, as ego_attn_bwd_* leaves it in the dq / dk slot) and receives
+ * d x in place; x = the RAW operand of the forward, mean / rstd its statistics; dw[64] += sum over slices of d y * xhat, through one
+ * partial row per workgroup in `work` (>= ego_headnorm_bwd_work_floats floats) summed in a fixed order: no float atomics, bitwise
+ * reproducible.  n_ops = 1, or 2 operands of the same B, n, H in one launch (q and k of one qkv buffer).  Nothing outside the
+ * B * n * H slices of 64 elements is written.  hd must be 64, pointers 16-byte aligned, strides multiples of 8, *_rs >= 64 H: else
+ * EGO_ERR_ARG.  A slice whose largest magnitude is >= 2^59 is normalised in a scaled domain (no overflow up to bf16's largest
+ * value); the backward needs |x - mean| finite in fp32. */
+typedef struct {
+    const void* x; long x_bs, x_rs;      /* bf16 source: the raw q or k */
+    void* y; long y_bs, y_rs;            /* forward: bf16 destination; backward: d y in, d x out */
+    const float* w;                      /* [64] */
+    float* mean; float* rstd;            /* [B * n * H] fp32: written by the forward, read by the backward */
+    float* dw;                           /* backward only: [64], accumulated */
+} ego_headnorm_op;
+int ego_headnorm_fwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, float eps, hipStream_t stream);
+long ego_headnorm_bwd_work_floats(int B, int n, int H, int n_ops);
+int ego_headnorm_bwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, float* work, long work_floats,
+                     hipStream_t stream);
 
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 inputs, fp32 MFMA accumulate.  Replaces F.linear under
  * autocast(bf16) (egom2p_utils.py:141-169, 180-203, 215-242; decoder_embeddings.py:372-383, 489-500)

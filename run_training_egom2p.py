@@ -56,6 +56,8 @@ def get_args(argv=None):
     p.add_argument("--num_target_tokens", default=2048, type=int)
     p.add_argument("--loss_type", default="mod")
     p.add_argument("--num_register_tokens", default=0, type=int)
+    p.add_argument("--qk_norm", action="store_true",
+                   help="per-head LayerNorm of q and k (the *_qknorm_nobias registrations' constructor keyword; dims with heads of 64)")
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "bf16"])
     p.add_argument("--opt", default="adamw")
     p.add_argument("--opt_eps", default=1e-8, type=float)
@@ -111,7 +113,7 @@ def get_model(args):
     dec = {m: MODALITY_INFO[m]["decoder_embedding"]() for m in args.out_domains}
     return create_model(args.model, encoder_embeddings=enc, decoder_embeddings=dec,
                         modality_info={m: MODALITY_INFO[m] for m in set(args.in_domains) | set(args.out_domains)},
-                        num_register_tokens=args.num_register_tokens)
+                        num_register_tokens=args.num_register_tokens, **(dict(qk_norm=True) if args.qk_norm else {}))
 
 
 class SyntheticClips:
