@@ -33,11 +33,10 @@ F32 = torch.float32
 I32 = torch.int32
 
 
-_PAIR_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
 _WARM_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
 
 
-def warmup_stream(dev: torch.device) -> "torch.cuda.Stream":
+def _warmup_stream(dev: torch.device) -> "torch.cuda.Stream":
     """The side stream graph captures warm up on: one per device and process (a stream is a hardware queue)."""
     key = dev.index if dev.index is not None else torch.cuda.current_device()
     if key not in _WARM_STREAMS:
@@ -113,6 +112,8 @@ class _Lin:
 
 
 class Engine:
+    pair_stream = None        # the benchmark reads and restores this around its per-kernel leg; it is always None
+
     def __init__(self, cfg: ModelCfg, device="cuda:0", max_batch: int = 1, n_enc: int = 2048, n_dec: int = 2048,
                  attn_o_residual: str = "cross", fp8_forward: bool = False, fp8_backward: bool = False):
         """attn_o_residual: which attention sites also keep the bf16 rounding residual of their output so that the
@@ -166,7 +167,7 @@ class Engine:
             raise NotImplementedError("mlp_bias with the gated MLP (a bias on the fused fc1||fc3 launch) is not built: mlp_bias needs mlp='gelu'")
         # the QK-norm family (egom2p_model.py:1122-1196; NormAttention / NormCrossAttention, egom2p_utils.py:247-332): a bias-free
         # LayerNorm over every head's 64 q and k values, one [64] weight per site and operand (ego_headnorm_fwd / _bwd)
-        self.qk_norm = bool(getattr(cfg, "qk_norm", False))
+        self.qk_norm = bool(cfg.qk_norm)
         if self.qk_norm and (self.padded or self.HD != 64):
             raise NotImplementedError("qk_norm is built for unpadded storage (dim % 128 == 0, heads of 64): the head-norm kernels take heads of 64")
         if self.qk_norm and (fp8_forward or fp8_backward):
@@ -179,38 +180,25 @@ class Engine:
         self.N, self.M, self.Bmax = n_enc, n_dec, max_batch
         # register tokens (egom2p_model.py:170-171, 381-387): R learned rows in front of every sample's N kept encoder tokens - the
         # encoder, the context and the cross-attention keys have Ne = R + N rows per sample; the compaction keeps N
-        self.R = int(getattr(cfg, "num_register_tokens", 0))
+        self.R = int(cfg.num_register_tokens)
         self.Ne = self.N + self.R
         self.scale = cfg.head_dim ** -0.5
         self._build_params()
+        self.q8, self.qs, self._q_of = None, None, None      # fp8 GEMMs: e4m3 copy + row scales of the current GEMM input, and whose it is
         self._alloc_workspaces()
         self.weights_dirty = True
         self._have_fwd = False
         self.fmods = self.mods                          # the modalities of the last forward (a mod_dict may hold a subset)
         self._ce_done, self._ce_grad = set(), None      # modalities whose CE backward ran inside the forward (loss_grad)
+        self._loss_mode = 0                             # ops.LOSS_MODES of the last forward
+        self._canon_dev = {}                            # decoder order -> its modality indices on the device
+        self.touched = None                             # track_touched_table_rows
         self.max_graphs = 16                  # captured generation passes kept alive at once (LRU)
         self._iw, self._infer_key = None, None
-        # optional: weight-gradient GEMMs on a side stream beside the dgrad / attention chain of the same layer, joined
-        # at every bucket boundary.  Measured on MI355X: parity-clean but 5 % SLOWER than one stream (the co-running
-        # kernels fight for LDS / L2), so it is off by default (EGOM2P_WGRAD_STREAM=1 enables it).
-        self.side = torch.cuda.Stream(device=self.dev) if os.environ.get("EGOM2P_WGRAD_STREAM", "0") == "1" else None
-        # optional (EGOM2P_WGRAD_PAIR=1): weight-gradient GEMMs paired with the LayerNorm backward launches (MFMA-bound beside
-        # HBM-bound, never two MFMA kernels at once): _ln_bwd.  Measured on MI355X: 191.1 vs 190.5 clips/s (two runs each, one
-        # box) - inside the noise: the LayerNorm backward already takes 5.4 TB/s and the GEMM's own 2.4 TB/s has nowhere to go.  Off.
-        self._pend, self.pair_stream = None, None
-        if self.side is None and os.environ.get("EGOM2P_WGRAD_PAIR", "0") == "1":
-            # ONE second stream per device and process (every torch.cuda.Stream() is another hardware queue; a long-lived process
-            # that builds many engines - the test suite - would otherwise oversubscribe the queues of a GPU it shares)
-            key = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-            if key not in _PAIR_STREAMS:
-                _PAIR_STREAMS[key] = torch.cuda.Stream(device=self.dev)
-            self.pair_stream = _PAIR_STREAMS[key]
-            self._pair_ev, self._pair_i = [torch.cuda.Event() for _ in range(16)], 0
         # decoder self-attention launched by row groups (one interval per workgroup); 0: per-row interval launches (round 3)
         self.attn_groups = os.environ.get("EGOM2P_ATTN_GROUPS", "1") != "0"
         self.attn_split = os.environ.get("EGOM2P_ATTN_SPLIT", "1") != "0"       # generation path: split keys on under-filled grids
         self.cfg_pair = os.environ.get("EGOM2P_CFG_PAIR", "1") != "0"           # guided step: cond + uncond share one decoder pass
-        self.gen_overlap = os.environ.get("EGOM2P_GEN_OVERLAP", "0") == "1"     # generation: independent launches on a second stream (_fork)
         # every decoder layer's context_norm normalises the SAME context tensor: one fused launch forward (x and its statistics
         # read once, one output per layer) and one backward (x once, one write of the context gradient) instead of one per layer
         # (the multi-layer launches have no biased twin: with norm_bias every layer's context_norm is its own launch)
@@ -222,72 +210,14 @@ class Engine:
         checkpoints and checked on load (a resume under another EGOM2P_HEAD_PAD must not die in a bare copy_)."""
         return (2, int(self.n_flat), int(self.D), int(self.Hs), int(self.HDP), int(self.Fp))    # 2: context_norm weights in one group (round 5)
 
-    # ---- generation path: independent launches of an under-filled pass beside each other (round 5) ----------------------------------
-    # At batch 1 the rgb -> depth passes are latency-bound (3414 decoder rows fill a third of the chip; the unconditional
-    # encoder group's self-attention is 324 workgroups for 768 slots), and several of their launches do not depend on each other:
-    # the cross-attention kv projections of ALL decoder layers depend only on the context, the two halves of a guided step's
-    # cross-attention and the two encoder groups' self-attention launches are independent.  They go to a second stream (fork / join
-    # by stream waits, which a hipGraph capture turns into parallel branches); EGOM2P_GEN_OVERLAP=0 keeps one stream.
-    def _fork(self, fn, which: int = 0):
-        """run fn on side stream `which` (0: the launch beside the current one, 1: the decoder's kv side chain - a long-lived
-        branch that must not sit in front of the short ones), ordered after everything issued on the current stream so far"""
-        if not self.gen_overlap:
-            fn()
-            return None
-        key = (self.dev.index if self.dev.index is not None else torch.cuda.current_device(), "gen", which)
-        if key not in _PAIR_STREAMS:
-            _PAIR_STREAMS[key] = torch.cuda.Stream(device=self.dev)      # (one per device and process: a stream is a hardware queue)
-        side, main = _PAIR_STREAMS[key], torch.cuda.current_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            fn()
-        return side
-
-    def _join(self, side):
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-
-    def _per_group(self, w, fn, n):
-        """fn(0) .. fn(n - 1): a generation pass's attention launches, one per group of samples.  Two groups with a second lane
-        (w["lse2"], _attn_infer): fn(1) goes out first, on the second stream, and runs beside fn(0)"""
-        beside = n == 2 and w.get("lse2") is not None
-        forked = self._fork(lambda: fn(1)) if beside else None
-        for g in range(n):
-            if not (beside and g == 1):
-                fn(g)
-        self._join(forked)
-
     def _ring_next(self):
         self._ring_i = (self._ring_i + 1) % len(self.ring_b)
         return self.ring_b[self._ring_i]
 
-    def _join_side(self):
-        if self._pend is not None:                 # paired mode: a weight gradient still held back goes out now
-            self._pend()
-            self._pend = None
-        if self.side is not None:
-            torch.cuda.current_stream().wait_stream(self.side)
-
     def _ln_bwd(self, dy, x, wname, st, dx_out, **kw):
-        """The backward of `_ln(x, wname, y, st)` (kw: dx_in, dx_bf16; dw and, with norm_bias, db are accumulated) - an HBM-bound
-        launch that leaves the MFMA pipes idle - with the weight-gradient GEMM that was held back (an MFMA-bound launch with no
-        consumer before the next bucket boundary) beside it on a second stream: the GEMM starts when the LayerNorm does, and the
-        main stream goes on only after both (two MFMA kernels never overlap: measured 5 - 26 % slower)."""
-        a = (dy, x, st[0], st[1], self.p[wname], dx_out, self.g[wname])
-        kw.update(width=self.Dl, db=self.g.get(wname[:-len("weight")] + "bias"))
-        run, self._pend = self._pend, None
-        if run is None:
-            return ops.layernorm_bwd(*a, **kw)
-        main = torch.cuda.current_stream()
-        e0, e1 = self._pair_ev[self._pair_i], self._pair_ev[self._pair_i + 1]
-        self._pair_i = (self._pair_i + 2) % len(self._pair_ev)
-        e0.record(main)
-        with torch.cuda.stream(self.pair_stream):
-            self.pair_stream.wait_event(e0)
-            run()
-            e1.record(self.pair_stream)
-        ops.layernorm_bwd(*a, **kw)
-        main.wait_event(e1)
+        """The backward of `_ln(x, wname, y, st)` (kw: dx_in, dx_bf16; dw and, with norm_bias, db are accumulated)"""
+        ops.layernorm_bwd(dy, x, st[0], st[1], self.p[wname], dx_out, self.g[wname], width=self.Dl,
+                          db=self.g.get(wname[:-len("weight")] + "bias"), **kw)
 
     # ------------------------------------------------------------------------------------ parameters
     def _build_params(self):
@@ -342,7 +272,7 @@ class Engine:
         marks.append(("mod_emb", len(spec)))
         for m in self.mods:
             add(f"encoder_embeddings.{m.name}.mod_emb", (D,))
-        if getattr(cfg, "num_register_tokens", 0):
+        if cfg.num_register_tokens:
             add("register_tokens", (cfg.num_register_tokens, D))       # reference shape (1, R, dim); decayed like mod_emb / mask_token
         for i in range(cfg.encoder_depth):
             marks.append((f"encoder.{i}", len(spec)))
@@ -736,7 +666,7 @@ class Engine:
                               b=self.p.get(wname[:-len("weight")] + "bias"))
 
     def _qbuf(self, rows, K):
-        if getattr(self, "q8", None) is None or self.q8.shape[0] < rows or self.q8.shape[1] < K:
+        if self.q8 is None or self.q8.shape[0] < rows or self.q8.shape[1] < K:
             self.q8 = torch.empty(rows, max(self.D, 3 * self.A, 2 * self.Fp), device=self.dev, dtype=torch.uint8)
             self.qs = torch.empty(rows, device=self.dev, dtype=F32)
         self._q_of = None
@@ -744,7 +674,7 @@ class Engine:
 
     def _quant(self, A, rows, K):
         """e4m3 copy of the first `rows` rows of A (row scales in self.qs); the buffers are reused by the next GEMM input"""
-        if getattr(self, "_q_of", None) == (A.data_ptr(), rows, K):      # the LayerNorm that made A already left its e4m3 copy
+        if self._q_of == (A.data_ptr(), rows, K):      # the LayerNorm that made A already left its e4m3 copy
             self._q_of = None
             return self.q8[:, :K]
         q = self._qbuf(rows, K)
@@ -794,26 +724,10 @@ class Engine:
         self._wgrad(l.g, dY, X, l.out_f, l.in_f, rows, ldp=dY.shape[-1], ldq=X.shape[-1])
 
     def _wgrad(self, G, dY, X, Ni, Nj, rows, ldp, ldq, m_range=None):
-        """G[Ni,Nj] += dY^T X on the side stream (operands must stay untouched until the next _join_side)."""
+        """G[Ni,Nj] += dY^T X"""
         splits = ops.tn_splits(Ni, Nj, rows, self.slab.numel(), ranged=m_range is not None, ldp=ldp, ldq=ldq)
-
-        def run():
-            ops.gemm_tn(dY, X, G, Ni, Nj, rows, m_range=m_range, splits=splits, slab=self.slab if splits > 1 else None,
-                        ldp=ldp, ldq=ldq, ldc=Nj)
-        if self.pair_stream is not None:
-            # paired mode: at most one weight-gradient GEMM is held back, to run beside the next LayerNorm backward (_ln_bwd);
-            # an older one goes out now, in launch order
-            if self._pend is not None:
-                self._pend()
-            self._pend = run
-        elif self.side is None:
-            run()
-        else:
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ev)
-                run()
+        ops.gemm_tn(dY, X, G, Ni, Nj, rows, m_range=m_range, splits=splits, slab=self.slab if splits > 1 else None,
+                    ldp=ldp, ldq=ldq, ldc=Nj)
 
     def _qkv_packed(self, t, r0=0):
         """(q, k, v) of a [rows, 3A] qkv buffer (or its gradient), from row r0 on"""
@@ -901,20 +815,18 @@ class Engine:
             s = 1
         return max(1, min(s, ((Nk + 63) // 64) // 4))         # at least four 64-key tiles per run
 
-    def _attn_infer(self, w, qkv, o_t, mask, B, Nq, Nk, lane=0):
-        """`_attn` of the generation passes: no LSE consumer, split keys when the grid is small.
-        lane = 1: a launch that runs BESIDE another attention launch (_fork): its own split scratch and LSE rows"""
+    def _attn_infer(self, w, qkv, o_t, mask, B, Nq, Nk):
+        """`_attn` of the generation passes: no LSE consumer, split keys when the grid is small"""
         sp = self._kv_splits(B, Nq, Nk)
-        wkey, lkey = ("att_ws", "lse") if lane == 0 else ("att_ws2", "lse2")
-        ws = w.get(wkey)
+        ws = w.get("att_ws")
         if sp > 1 and ws is not None and ws.numel() < ops.attn_fwd_split_floats(B, self.Hs, Nq, sp) and not torch.cuda.is_current_stream_capturing():
-            ws = w[wkey] = torch.empty(ops.attn_fwd_split_floats(B, self.Hs, Nq, sp) + 4096, device=self.dev, dtype=F32)
+            ws = w["att_ws"] = torch.empty(ops.attn_fwd_split_floats(B, self.Hs, Nq, sp) + 4096, device=self.dev, dtype=F32)
         if sp > 1 and ws is not None and ws.numel() >= ops.attn_fwd_split_floats(B, self.Hs, Nq, sp):
             q, k, v = qkv
-            ops.attn_fwd_split(*q.args(Nq), *k.args(Nk), *v.args(Nk), *_Rows(o_t, 0, self.A).args(Nq), w[lkey], *mask,
+            ops.attn_fwd_split(*q.args(Nq), *k.args(Nk), *v.args(Nk), *_Rows(o_t, 0, self.A).args(Nq), w["lse"], *mask,
                                B, self.Hs, Nq, Nk, self.scale, sp, ws)
         else:
-            self._attn(qkv, o_t, w[lkey], mask, B, Nq, Nk)
+            self._attn(qkv, o_t, w["lse"], mask, B, Nq, Nk)
 
     def _dec_groups(self):
         """Row groups of the decoder's block-diagonal self-attention mask for the attention kernels (head dim 64): the
@@ -1007,10 +919,9 @@ class Engine:
         ops.embed_fwd(None, [self.pos[m.name] for m in dmods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in dmods],
                       self.p["mask_token"], cd["slot"], cd["local"], cd["tok"], y0, None, RM, D)
         ckey = tuple(m.name for m in dmods)
-        cache = self.__dict__.setdefault("_canon_dev", {})
-        if ckey not in cache:                        # one small H2D copy per decoder order, ever (never inside a graph capture)
-            cache[ckey] = torch.tensor([mods.index(m) for m in dmods], dtype=I32).to(self.dev)
-        self.canon[:n_mods].copy_(cache[ckey])
+        if ckey not in self._canon_dev:              # one small H2D copy per decoder order, ever (never inside a graph capture)
+            self._canon_dev[ckey] = torch.tensor([mods.index(m) for m in dmods], dtype=I32).to(self.dev)
+        self.canon[:n_mods].copy_(self._canon_dev[ckey])
         ops.loss_perm(cd["seg"], self.canon, cd["slot"], cd["tok"], B, M, n_mods, self.perm, self.tgt_perm,
                       self.ranges, self.perm_base)
 
@@ -1126,7 +1037,7 @@ class Engine:
         cfg, D, N, M, B = self.cfg, self.D, self.Ne, self.M, self.B       # N: encoder rows per sample (registers included)
         RN, RM = B * N, B * M
         mods, ce, cd = self.fmods, self.ce, self.cd           # the modalities of the forward (absent ones: no kernel writes their gradients)
-        if getattr(self, "_ce_done", None):
+        if self._ce_done:
             # the forward already turned the logits into d logits with the upstream gradient it was promised
             same = (gscale is self._ce_grad) or (not isinstance(gscale, torch.Tensor) and not isinstance(self._ce_grad, torch.Tensor)
                                                  and float(gscale) == float(self._ce_grad))
@@ -1138,7 +1049,6 @@ class Engine:
         enc_keys = _keys_per_sample(self.zero_b, ce["n_valid"])             # the encoder rows as keys: self- and cross-attention
 
         def done(name):
-            self._join_side()          # the bucket's weight gradients come from the side stream
             if bucket_done is not None:
                 lo, hi = bmap[name]
                 bucket_done(name, lo, hi)
@@ -1151,7 +1061,7 @@ class Engine:
             lg = self.logits[V]
             if c not in self._ce_done:
                 ops.ce_bwd(lg, V, V, self.tgt_perm, self.ranges[c], ub, self.lse_ce, self.gscale, len(mods),
-                           loss_w=self.loss_w[c:c + 1] if getattr(self, "_loss_mode", 0) else None)
+                           loss_w=self.loss_w[c:c + 1] if self._loss_mode else None)
             ops.gemm_nt(lg, l.wt, self.dyn, ub, D, V, L.EPI_BF16, m_range=self.ranges[c], lda=V, ldb=V, ldc=D)
             self._wgrad(l.g, lg, self.yn, V, D, ub, ldp=V, ldq=D, m_range=self.ranges[c])
         for m in reversed(self.mods):                          # (every bucket is handed over, an absent modality's with zeros)
@@ -1181,7 +1091,7 @@ class Engine:
             nb = self._ring_next()
             self._ln_bwd(dln, w["x1"][:RM], f"{pre}.query_norm.weight", w["stq"], dres, dx_in=dres, dx_bf16=nb)
             dres_b = nb
-            dcn = self.dcn[i] if fused else self.t_d3    # not t_d2: dq is still being read by the q-projection wgrad on the side stream
+            dcn = self.dcn[i] if fused else self.t_d3    # t_d3 and not t_d2: kept so that buffer use and results stay what they were
             self._lin_bwd(f"{pre}.cross_attn.kv.weight", dkv, w["cn"], dcn, RN)
             if not fused:
                 self._ln_bwd(dcn, self.ctx[:RN], f"{pre}.context_norm.weight", w["stc"], self.dctx, dx_in=None if first_ctx else self.dctx)
@@ -1227,13 +1137,12 @@ class Engine:
         ops.embed_bwd([self.g[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
                       [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, dxe, self.dctx,
                       ce["slot"], ce["tok"], RN, D,
-                      touched=None if getattr(self, "touched", None) is None else [self.touched[self.mods.index(m)] for m in mods])
+                      touched=None if self.touched is None else [self.touched[self.mods.index(m)] for m in mods])
         if self.R:        # d register_tokens = the encoder input gradient of the register rows, summed over the batch (emb is 0 there)
             ops.reg_grad(dxe, B, N, self.R, D, self.g["register_tokens"])
         done("mod_emb")
         for m in reversed(self.mods):
             done(f"enc_table.{m.name}")
-        self._join_side()
         self._have_fwd = False
         self._ce_done = set()
 
@@ -1308,12 +1217,6 @@ class Engine:
                     if sp_ > 1:
                         need = max(need, int(ops.attn_fwd_split_floats(b_, H, nq_, sp_)))
         w["att_ws"] = e(need + 4096, dt=F32) if (self.HDP == 64 and self.attn_split) else None
-        # a second attention launch beside the first (_fork): its own scratch and LSE rows; one kv buffer per decoder layer when the
-        # kv projections run as a side chain
-        w["att_ws2"] = (e(need + 4096, dt=F32) if (self.HDP == 64 and self.attn_split and G > 1 and self.gen_overlap) else None)
-        w["lse2"] = e(G * B, H, max(Nmax, Mmax), dt=F32) if (G > 1 and self.gen_overlap) else None
-        w["st2"] = e(2, RC, dt=F32) if self.gen_overlap else None
-        w["kvs"] = ([e(RC, 2 * A) for _ in range(self.cfg.decoder_depth)] if (self.gen_overlap and self.ctx_ln_fused) else None)
         if not fresh:
             self._iw, self._infer_key = w, key
         return w
@@ -1337,15 +1240,13 @@ class Engine:
                           [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, side["slot"], side["local"], side["tok"],
                           x[r0:], w["emb"][r0:], B * N, D, reg=self.p["register_tokens"] if self.R else None)
 
-        def enc_attn(gi):
-            side, _, N, r0 = parts[gi]
-            self._attn_infer(w, self._qkv_site(w, r0), w["ao"][r0:], _keys_per_sample(w["zero_b"], side["n_valid"]), B, N, N,
-                             lane=1 if (gi == 1 and w.get("lse2") is not None) else 0)
+        def enc_attn():
+            for side, _, N, r0 in parts:
+                self._attn_infer(w, self._qkv_site(w, r0), w["ao"][r0:], _keys_per_sample(w["zero_b"], side["n_valid"]), B, N, N)
 
         for i in range(cfg.encoder_depth):
             pre = f"encoder.{i}"
-            # (the second group - the unconditional inputs: 324 workgroups at 3414 rows - beside the first group's launch)
-            self._attn_sublayer(pre, "attn", x, xn, R, w["ln"], w["st"], w["qkv"], w["ao"], lambda: self._per_group(w, enc_attn, len(parts)), w=w)
+            self._attn_sublayer(pre, "attn", x, xn, R, w["ln"], w["st"], w["qkv"], w["ao"], enc_attn, w=w)
             self._mlp_sublayer(pre, xn, x, R, w["ln"], w["st"], w["ab"], w["h"])
         self._ln(x[:R], "encoder_norm.weight", w["ln"], w["st"])
         self._lin_fwd("decoder_proj_context.weight", w["ln"], w["ctx"], R, L.EPI_BIAS_RESID, R=w["emb"],
@@ -1374,22 +1275,7 @@ class Engine:
         w["full_m"].fill_(M)
         all_keys = _keys_per_sample(w["zero_b"], w["full_m"])       # decoder self-attention is unmasked (sa_mask=None)
         fused = self.ctx_ln_fused and w.get("cns") is not None and RC > 0
-        kv_side, kv_evs = None, None
-        if fused and w.get("kvs") is not None and RQ > 0:
-            # side chain: every layer's context LayerNorm output (one fused launch) and kv projection depend on the context only -
-            # they run on the second stream beside the decoder's self-attention blocks; layer i's cross-attention waits for kv i
-            kv_evs = [torch.cuda.Event() for _ in range(cfg.decoder_depth)]
-
-            def chain():
-                ops.layernorm_fwd_multi(w["ctx"][:RC], [self.p[f"decoder.{i}.context_norm.weight"] for i in range(cfg.decoder_depth)],
-                                        w["cns"], w["st2"][0], w["st2"][1], eps=cfg.eps, width=self.Dl)
-                for i in range(cfg.decoder_depth):
-                    self._lin_fwd(f"decoder.{i}.cross_attn.kv.weight", w["cns"][i], w["kvs"][i], RC)
-                    kv_evs[i].record(torch.cuda.current_stream())
-            kv_side = self._fork(chain, which=1)
-            if kv_side is None:
-                kv_evs = None
-        elif fused:
+        if fused:
             ops.layernorm_fwd_multi(w["ctx"][:RC], [self.p[f"decoder.{i}.context_norm.weight"] for i in range(cfg.decoder_depth)],
                                     w["cns"], w["st"][0], w["st"][1], eps=cfg.eps, width=self.Dl)
         for i in range(cfg.decoder_depth):
@@ -1401,25 +1287,16 @@ class Engine:
                 self._ln(yn[:RQ], f"{pre}.query_norm.weight", w["ln"], w["st"])
                 self._lin_fwd(f"{pre}.cross_attn.q.weight", w["ln"], w["q"], RQ)
                 cn = w["cns"][i] if fused else w["cn"]
-                kvb = w["kv"]
-                if kv_side is not None or (fused and w.get("kvs") is not None and RQ > 0):
-                    kvb = w["kvs"][i]                          # made by the side chain (or, one stream: in line, at the top)
-                    if kv_evs is not None:
-                        torch.cuda.current_stream().wait_event(kv_evs[i])
-                else:
-                    if not fused:
-                        self._ln(w["ctx"][:RC], f"{pre}.context_norm.weight", cn, w["st"])
-                    self._lin_fwd(f"{pre}.cross_attn.kv.weight", cn, kvb, RC)
-
+                if not fused:
+                    self._ln(w["ctx"][:RC], f"{pre}.context_norm.weight", cn, w["st"])
+                self._lin_fwd(f"{pre}.cross_attn.kv.weight", cn, w["kv"], RC)
                 if self.qk_norm:
                     self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RQ)
-                    self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(kvb, 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RC)
-
-                def cross(g):
+                    self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RC)
+                for g in range(n_ctx):                          # the two halves of a guided step attend different contexts
                     side, n, c0 = parts[g]
-                    self._attn_infer(w, self._q_kv_site(w, kvb, g * RM, c0), w["ao"][g * RM:], _keys_per_sample(w["zero_b"], side["n_valid"]),
-                                     B, M, n, lane=1 if (g == 1 and w.get("lse2") is not None) else 0)
-                self._per_group(w, cross, n_ctx)                # the two halves of a guided step attend different contexts
+                    self._attn_infer(w, self._q_kv_site(w, w["kv"], g * RM, c0), w["ao"][g * RM:], _keys_per_sample(w["zero_b"], side["n_valid"]),
+                                     B, M, n)
                 rows_p = RQ
                 if RQ < RD and proj_b:
                     w["ao"][RQ:RD].zero_()                     # groups without a context: proj(0) = its bias (below)
@@ -1437,7 +1314,6 @@ class Engine:
                 y, yn = yn, y
             self._mlp_sublayer(pre, y, yn, RD, w["ln"], w["st"], w["ab"], w["h"])
             y, yn = yn, y
-        self._join(kv_side)                                  # (every kv event has been waited for; a capture wants the branch joined)
         self._ln(y[:RD], "decoder_norm.weight", w["ln"], w["st"])
         l = self.lin[self.logit_key[tm.name]]
         logits = out if out is not None else torch.empty(RD, tm.vocab_size, device=self.dev, dtype=BF16)
@@ -1491,7 +1367,10 @@ class Engine:
 
     def _graphed(self, key, make_state, run):
         """Capture-once / replay cache of the generation passes: `make_state()` builds the static buffers (a captured
-        graph bakes in device addresses: it owns its workspace for as long as it lives), `run(st)` issues the launches."""
+        graph bakes in device addresses: it owns its workspace for as long as it lives), `run(st)` issues the launches.
+        A graph reads the bf16 weight copies in place: they are refreshed here, before a capture and before every replay."""
+        if self.weights_dirty:
+            self.refresh_weights()
         graphs = self.__dict__.setdefault("_graphs", {})
         g = graphs.pop(key, None)
         if g is None:
@@ -1500,7 +1379,7 @@ class Engine:
             while len(graphs) >= self.max_graphs:
                 graphs.pop(next(iter(graphs)))
             st = make_state()
-            side = warmup_stream(self.dev)
+            side = _warmup_stream(self.dev)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                           # warm-up (lazy inits happen here, not in the capture)
                 run(st)
@@ -1516,8 +1395,6 @@ class Engine:
         """The graphed generation passes: static copies of the input sets (modality -> (ids, mask)) and of dec_pos, a captured
         `run(ws, static sets, static dec_pos, out)` over them (`_graphed`, keyed by key(modality names)), then copy-in and replay.
         Returns the static bf16 logits [len(sets) * B * M, V]: valid until the next replay of the same graph."""
-        if self.weights_dirty:
-            self.refresh_weights()
         B, M = dec_pos.shape
         names = tuple(m.name for m in self.mods if m.name in sets[0])
 

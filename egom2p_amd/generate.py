@@ -33,7 +33,6 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import warmup_stream
 
 
 # ---------------------------------------------------------------------------------------------- schedules
@@ -375,44 +374,29 @@ class GenerationSampler:
         #  minus what earlier steps committed - follow from those two, so they need no entry of their own)
         if "maskgit" in schemes:                                # (ROAR-only schedules keep the key they always had)
             key = key + (tuple(schemes),)
-        graphs = eng.__dict__.setdefault("_graphs", {})
-        g = graphs.pop(key, None)
-        if g is None:
-            while len(graphs) >= eng.max_graphs:
-                graphs.pop(next(iter(graphs)))
-            if eng.weights_dirty:
-                eng.refresh_weights()
-            n_max = max(max(p["n_enc_cond"] for p in plan), 1) + getattr(eng, "R", 0)
+
+        def make_state():
+            n_max = max(max(p["n_enc_cond"] for p in plan), 1) + eng.R
             m_max = max(p["n_rows"] for p in plan)
-            st = {"in": {n: {k: v.clone() for k, v in flat[n].items()} for n in names},
-                  "noise": [torch.zeros(flat[p["target"]]["target_mask"].shape[1], device=eng.dev) for p in plan],
-                  "uni": [torch.zeros(B * p["n_rows"], device=eng.dev) for p in plan],
-                  "ws": eng._alloc_infer(B, n_max, m_max, fresh=True,
-                                         groups=2 if (eng.cfg_pair and any(p["guided"] for p in plan)) else 1), "out": None}
+            return {"in": {n: {k: v.clone() for k, v in flat[n].items()} for n in names},
+                    "noise": [torch.zeros(flat[p["target"]]["target_mask"].shape[1], device=eng.dev) for p in plan],
+                    "uni": [torch.zeros(B * p["n_rows"], device=eng.dev) for p in plan],
+                    "ws": eng._alloc_infer(B, n_max, m_max, fresh=True,
+                                           groups=2 if (eng.cfg_pair and any(p["guided"] for p in plan)) else 1), "out": None}
 
-            def run():
-                md = {n: {k: v.clone() for k, v in st["in"][n].items()} for n in names}
-                for i, p in enumerate(plan):
-                    info = p["info"]
-                    step = self.roar_step if p["scheme"] == "roar" else self.maskgit_step
-                    md = step(md, p["target"], p["n_dec"], info["temperature"], top_k, top_p,
-                              conditioning=info.get("cfg_cond_domains", []), guidance_scale=info.get("cfg_scale", 1.0),
-                              uniforms=st["uni"][i],
-                              static=dict(noise=st["noise"][i], n_dec=p["n_rows"], n_enc_cond=p["n_enc_cond"],
-                                          n_enc_uncond=p["n_enc_uncond"], ws=st["ws"]))
-                return md
+        def run(st):
+            md = {n: {k: v.clone() for k, v in st["in"][n].items()} for n in names}
+            for i, p in enumerate(plan):
+                info = p["info"]
+                step = self.roar_step if p["scheme"] == "roar" else self.maskgit_step
+                md = step(md, p["target"], p["n_dec"], info["temperature"], top_k, top_p,
+                          conditioning=info.get("cfg_cond_domains", []), guidance_scale=info.get("cfg_scale", 1.0),
+                          uniforms=st["uni"][i],
+                          static=dict(noise=st["noise"][i], n_dec=p["n_rows"], n_enc_cond=p["n_enc_cond"],
+                                      n_enc_uncond=p["n_enc_uncond"], ws=st["ws"]))
+            st["out"] = md                                      # (the capture's run comes last: its tensors are the graph's)
 
-            side = warmup_stream(eng.dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                       # warm-up outside the capture (lazy initialisations)
-                run()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                st["out"] = run()
-            g = (graph, st)
-        graphs[key] = g
-        graph, st = g
+        graph, st = eng._graphed(key, make_state, run)
         for n in names:
             for k in ("tensor", "input_mask", "target_mask"):
                 st["in"][n][k].copy_(flat[n][k])

@@ -447,3 +447,33 @@ def test_invalid_loss_type_is_the_reference_error():
     eng = Engine(cfg, "cuda:0", max_batch=1, n_enc=30, n_dec=30)
     with pytest.raises(ValueError, match="Invalid loss type"):
         eng.forward({}, loss_type="tokens")
+
+
+def test_training_and_generation_run_on_one_stream(monkeypatch):
+    """A training step and a guided generation pass create no stream: every launch goes to the caller's current one (each
+    `torch.cuda.Stream()` is another hardware queue of a device that may be shared)."""
+    cfg = MODEL_CFGS["ego_gen_384_2e_2d"]
+    eng = Engine(cfg, "cuda:0", max_batch=2, n_enc=64, n_dec=64)
+    eng.init_random(3)
+    md = synth.make_clip_batch_device(cfg, 2, synth.dirichlet_budgets(cfg, 2, 64, 64, 4), seed=4, sample_offset=0, device="cuda:0")
+    rgb = synth.randint("one.rgb", (2, 5120), 64000, seed=1).to("cuda:0")
+    keep = torch.ones(2, 5120, dtype=torch.bool, device="cuda:0")
+    keep[:, :200] = False                                                       # 200 inputs kept
+    enc_c, enc_u = {"tok_rgb": (rgb, keep)}, {"tok_rgb": (rgb, torch.ones_like(keep))}
+    pos = torch.arange(100, device="cuda:0")[None].repeat(2, 1)
+    made, init = [], torch.cuda.Stream.__init__
+
+    def counted(self, *a, **kw):
+        if "stream_id" not in kw:                   # (with it: a handle of an existing stream - torch.cuda.current_stream() builds one per call)
+            made.append(1)
+        if init is not object.__init__:                                         # (object's takes no arguments and does nothing)
+            init(self, *a, **kw)
+
+    monkeypatch.setattr(torch.cuda.Stream, "__init__", counted)
+    eng.zero_grad()
+    loss, _ = eng.forward(md, dec_order=[m.name for m in cfg.mods])
+    eng.backward(1.0)
+    lc, lu = eng.infer_logits_cfg(enc_c, 200, enc_u, 0, "tok_depth", pos)
+    torch.cuda.synchronize()
+    assert torch.isfinite(loss) and torch.isfinite(lc.float()).all() and torch.isfinite(lu.float()).all()
+    assert len(made) == 0

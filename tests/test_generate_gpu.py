@@ -367,3 +367,33 @@ def test_whole_schedule_graph_matches_eager_generation(cfg_name, cond, target, n
             b = graphed.generate_graphed(sample, sch, top_p=0.8, top_k=tk, seed=3)
             assert torch.equal(a[target]["tensor"], b[target]["tensor"]), tk
         assert sum(1 for k in eng._graphs if k[0] == "generate") == 3
+
+
+def test_graphed_generation_follows_a_weight_update():
+    """A cached graph reads the engine's bf16 weight copies in place: after `load_state_dict` (or an optimiser step) both graphed
+    forms - the whole schedule as one graph, and one graph per pass - replay against the refreshed copies and give the eager
+    path's tokens, bit for bit, from the graphs they already had (nothing is captured again)."""
+    cfg = MODEL_CFGS["ego_gen_384_2e_2d"]
+    eng = Engine(cfg, "cuda:0", max_batch=2, n_enc=64, n_dec=64)
+    eng.init_random(3)
+    sample = {"tok_rgb": {"tensor": synth.randint("stale.rgb", (1, 5, 32, 32), 64000, seed=2).to(DEV)}}
+    sample = init_empty_target_modality(sample, MODALITY_INFO, "tok_depth", 1, 5120, DEV)
+    sample = init_full_input_modality(sample, MODALITY_INFO, "tok_rgb", DEV)
+    sch = build_chained_generation_schedules(["tok_rgb"], ["tok_depth"], [5120], ["roar"], [3], ["linear"], [0.01], ["constant"],
+                                             [2.0], ["constant"], cfg_grow_conditioning=True)
+    eager, per_pass = GenerationSampler(eng, use_graphs=False), GenerationSampler(eng, use_graphs=True)
+
+    def tokens(out):
+        return out["tok_depth"]["tensor"]
+
+    old = tokens(per_pass.generate_graphed(sample, sch, top_p=0.8, seed=7)).clone()       # captures
+    assert torch.equal(tokens(per_pass.generate(sample, sch, top_p=0.8, seed=7)), old)    # captures one graph per pass
+    n_graphs = len(eng._graphs)
+    eng.load_state_dict(synth.build_state_dict(cfg, 5))
+    whole = tokens(per_pass.generate_graphed(sample, sch, top_p=0.8, seed=7)).clone()     # (first: nothing else has refreshed the copies)
+    passes = tokens(per_pass.generate(sample, sch, top_p=0.8, seed=7)).clone()
+    want = tokens(eager.generate(sample, sch, top_p=0.8, seed=7))
+    assert not torch.equal(want, old)                                                     # the update changes the tokens
+    assert torch.equal(whole, want)
+    assert torch.equal(passes, want)
+    assert sum(1 for k in eng._graphs if k[0] == "generate") == 1 and len(eng._graphs) == n_graphs      # reused, not recaptured
