@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EGOM2P_HIP_LIB", os.path.join(_HERE, "libegom2p_hip.so"))   # override: kernel experiments
 MAX_MODS = 8
 
-ABI_VERSION = 11         # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
+ABI_VERSION = 12         # == EGO_ABI_VERSION of include/egom2p_hip.h (tests/test_cabi_exports.py holds the two together)
 EPI_BF16, EPI_F32, EPI_RESID, EPI_BIAS_RESID, EPI_BIAS_BF16 = 0, 1, 2, 3, 4
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_float
@@ -87,6 +87,9 @@ _SIGS = {
     "ego_headnorm_fwd": [C.POINTER(HeadNormOp), i32, i32, i32, i32, i32, f32, vp],
     "ego_headnorm_bwd_work_floats": [i32, i32, i32, i32],
     "ego_headnorm_bwd": [C.POINTER(HeadNormOp), i32, i32, i32, i32, i32, vp, i64, vp],
+    "ego_droppath_draw": [vp, i32, i32, C.c_uint64, C.c_uint64, vp, vp],
+    "ego_droppath_resid": [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32, vp],
+    "ego_droppath_scale": [vp, i64, vp, i64, vp, i64, i32, i32, i32, f32, vp],
     "ego_gemm_nt_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp],
     "ego_gemm_tn_bf16": [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp],
     "ego_quant_fp8_rows": [vp, i64, i64, i32, vp, i64, vp, vp],

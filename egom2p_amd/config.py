@@ -65,6 +65,11 @@ class ModelCfg:
     mlp_bias: bool = False             # bias of fc1 / fc2
     norm_bias: bool = False            # LayerNorm with its bias (nn.LayerNorm; egom2p_utils.py:118-133)
     qk_norm: bool = False              # per-head LayerNorm(head_dim) of q and k in every attention site (NormAttention / NormCrossAttention, egom2p_utils.py:247-332)
+    # stochastic depth (egom2p_model.py:96-98, 137-154): the last layer's drop rate of either stack, the layers' rates a linspace from 0
+    # (shared_drop_path: ONE linspace over encoder + decoder layers); a training-time regulariser that owns no parameters
+    drop_path_rate_encoder: float = 0.0
+    drop_path_rate_decoder: float = 0.0
+    shared_drop_path: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -116,6 +121,10 @@ MODEL_CFGS: Dict[str, ModelCfg] = {
     # the registered base geometry at full depth (`bench.py --model ego_b_qknorm`)
     "ego_384_2e_2d_qknorm": ModelCfg("ego_384_2e_2d_qknorm", 384, 2, 2, 6, qk_norm=True),
     "ego_gen_384_2e_2d_qknorm": ModelCfg("ego_gen_384_2e_2d_qknorm", 384, 2, 2, 6, modalities=("tok_rgb", "tok_depth"), qk_norm=True),
+    # stochastic depth (drop_path_rate_encoder = drop_path_rate_decoder = 0.3 under shared_drop_path: per-layer rates 0, 0.1 | 0.2, 0.3) at
+    # the tiny variant's width and parity-test depth: tests/golden/b2_droppath.npz
+    "ego_384_2e_2d_droppath": ModelCfg("ego_384_2e_2d_droppath", 384, 2, 2, 6, drop_path_rate_encoder=0.3, drop_path_rate_decoder=0.3,
+                                       shared_drop_path=True),
     "ego_b_qknorm": ModelCfg("ego_b_qknorm", 768, 12, 12, 12, qk_norm=True),
     "ego_L_1152": ModelCfg("ego_L_1152", 1152, 24, 24, 18),
     "ego_L_1152_2e_2d": ModelCfg("ego_L_1152_2e_2d", 1152, 2, 2, 18),       # ego-L width (BASELINE config 5) at parity-test depth

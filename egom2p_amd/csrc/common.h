@@ -43,6 +43,15 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float round_bf16(float f) { return bf16_to_f32(f32_to_bf16(f)); }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
+// The project's counter-based generator (mask.hip: clip synthesis and token budgets; droppath.hip: the drop-path decisions):
+// splitmix64 of key + i * golden - a pure function of (key, i), restated on the host in integers (egom2p_amd/synth.py)
+__device__ __forceinline__ uint64_t splitmix(uint64_t key, uint64_t i) {
+    uint64_t x = i * 0x9E3779B97F4A7C15ull + key;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // Wave-wide reductions on the VALU: four DPP steps (quad swaps, half-row mirror, row mirror) leave every lane of a 16-lane
 // row with the row's result, four v_readlane + scalar-operand ops join the rows.  (__shfl_xor compiles to ds_bpermute_b32:
 // six dependent LDS round trips per reduction, each behind an lgkmcnt(0) - on the critical path of every LayerNorm row and of

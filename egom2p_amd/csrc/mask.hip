@@ -17,13 +17,6 @@ namespace {
 
 constexpr int SYN_MAX_N = 8192;
 
-__device__ __forceinline__ uint64_t splitmix(uint64_t key, uint64_t i) {
-    uint64_t x = i * 0x9E3779B97F4A7C15ull + key;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 __global__ __launch_bounds__(1024) void clip_synth_kernel(const uint64_t* __restrict__ key_ids, const uint64_t* __restrict__ key_perm,
                                                           const int* __restrict__ k_in, const int* __restrict__ k_tgt, int n, int vocab,
                                                           long* __restrict__ ids, unsigned char* __restrict__ in_mask,

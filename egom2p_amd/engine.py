@@ -64,6 +64,17 @@ def head_layout(H: int, HD: int, min_pad: int = 0) -> Tuple[int, int]:
     return fits[0][1], fits[0][0] // fits[0][1]
 
 
+def drop_path_rates(cfg: ModelCfg) -> Tuple[List[float], List[float]]:
+    """Per-layer drop rates (encoder, decoder) by the reference's rule (egom2p_model.py:137-154): the fp32 `.item()` values of
+    torch.linspace(0, rate, depth) per stack or, with shared_drop_path, of ONE linspace over encoder + decoder layers cut at the
+    encoder depth.  A layer at rate 0 (always the first of a linspace from 0) holds nn.Identity there: it neither scales nor draws."""
+    Le, Ld = cfg.encoder_depth, cfg.decoder_depth
+    re_, rd = float(cfg.drop_path_rate_encoder), float(cfg.drop_path_rate_decoder)
+    if cfg.shared_drop_path:
+        return ([v.item() for v in torch.linspace(0, re_, Le + Ld)][:Le], [v.item() for v in torch.linspace(0, rd, Le + Ld)][Le:])
+    return [v.item() for v in torch.linspace(0, re_, Le)], [v.item() for v in torch.linspace(0, rd, Ld)]
+
+
 def _pad128(n: int) -> int:
     return (n + 127) // 128 * 128
 
@@ -175,6 +186,22 @@ class Engine:
         if self.qk_norm and self.norm_bias:
             raise NotImplementedError("qk_norm with norm_bias=True (the reference then gives the head norms a bias) is not built")
         self.Fab = self.Fp if self.gelu else 2 * self.Fp        # width of the saved MLP pre-activation rows: u, or a || b
+        # stochastic depth (egom2p_utils.py:89-112, 356-359, 387-391): the residual sites with a non-zero rate, in forward order - (site
+        # name, keep_prob as the fp32 the reference's bf16 `x.div(keep_prob)` divides by).  No site: nothing below allocates or launches.
+        r_enc, r_dec = drop_path_rates(cfg)
+        for r in r_enc + r_dec:
+            if not 0.0 <= r < 1.0:
+                raise ValueError(f"drop path rates must lie in [0, 1), not {r}")
+        self.dp_sites: List[Tuple[str, float]] = []
+        for kind, rates, subs in (("encoder", r_enc, ("attn", "mlp")), ("decoder", r_dec, ("self_attn", "cross_attn", "mlp"))):
+            for i, r in enumerate(rates):
+                if r > 0.0:
+                    kp = torch.tensor(1.0 - r, dtype=torch.float64).to(F32).item()
+                    self.dp_sites += [(f"{kind}.{i}.{sub}", kp) for sub in subs]
+        self._dp_ix = {name: (j, kp) for j, (name, kp) in enumerate(self.dp_sites)}
+        self._dp_live = False                 # the forward in flight / being differentiated drops paths
+        self._dp_seed, self._dp_counter, self._dp_inject = 0, 0, None
+        self.dp_last = None                   # (seed, forward counter) the last training forward drew with; None: injected tables
         self.mods: List[Modality] = cfg.mods
         self.n_mods = len(self.mods)
         self.N, self.M, self.Bmax = n_enc, n_dec, max_batch
@@ -650,6 +677,85 @@ class Engine:
             self.q8 = e(R, max(D, 3 * A, 2 * Fp), dt=torch.uint8)
             self.qs = e(R, dt=F32)
         self.gscale = torch.ones(1, device=dev, dtype=F32)
+        if self.dp_sites:
+            self.dp_kp = torch.tensor([kp for _, kp in self.dp_sites], dtype=F32).to(dev)
+            self.dp_keep = torch.ones(len(self.dp_sites) * B, device=dev, dtype=torch.uint8)     # [n_sites, B of the forward] decisions
+            self.dp_branch = e(R, D)          # a site's branch: the bf16 its last linear leaves in front of ego_droppath_resid
+            self.dp_g = e(R, D)               # a site's scaled upstream gradient (ego_droppath_scale of the residual gradient)
+
+    # ------------------------------------------------------------------------------------ stochastic depth
+    def set_drop_path_seed(self, seed: int, counter: int = 0):
+        """The stream the drop-path decisions are drawn from: training forward number `counter` of stream `seed` draws, on the device,
+        keep(site s, sample b) = top 24 bits of splitmix(splitmix(splitmix(seed, counter), s), b) < floor(keep_prob[s] * 2^24), and the
+        counter advances by one per training forward (micro-batches of one step differ).  Ranks use seed + rank; a resumed run sets
+        the counter to its loader-step position."""
+        self._dp_seed, self._dp_counter = int(seed), int(counter)
+
+    def inject_drop_path(self, encoder=None, decoder=None):
+        """TEST HOOK: the keep tables of the NEXT training forward (and of its backward) instead of a draw - encoder bool [Le, 2, B]
+        (attn, mlp), decoder bool [Ld, 3, B] (self_attn, cross_attn, mlp), True = the sample keeps the branch; a missing table keeps
+        everything.  Entries of sites with rate 0 are ignored (those sites hold no drop path).  The forward counter does not advance."""
+        self._dp_inject = (encoder, decoder)
+
+    def drop_path_table(self) -> Optional[torch.Tensor]:
+        """The decisions the last training forward used: uint8 [n_sites, B] in `dp_sites` order (a copy); None without one"""
+        if not self.dp_sites or not self._dp_live:
+            return None
+        return self.dp_keep[:len(self.dp_sites) * self.B].view(len(self.dp_sites), self.B).clone()
+
+    def _dp_begin(self, training: bool, B: int):
+        """The decisions of the forward that starts: one ego_droppath_draw launch for all sites, or the injected tables"""
+        self._dp_live = bool(training and self.dp_sites)
+        inject, self._dp_inject = self._dp_inject, None
+        if not self._dp_live:
+            return
+        n = len(self.dp_sites)
+        if inject is not None:
+            tab = torch.ones(n, B, dtype=torch.uint8)
+            for kind, t, subs in (("encoder", inject[0], ("attn", "mlp")), ("decoder", inject[1], ("self_attn", "cross_attn", "mlp"))):
+                if t is None:
+                    continue
+                t = torch.as_tensor(t).cpu()
+                depth = self.cfg.encoder_depth if kind == "encoder" else self.cfg.decoder_depth
+                if tuple(t.shape) != (depth, len(subs), B):
+                    raise ValueError(f"inject_drop_path: the {kind} table must be [{depth}, {len(subs)}, {B}], not {tuple(t.shape)}")
+                for i in range(depth):
+                    for j, sub in enumerate(subs):
+                        if f"{kind}.{i}.{sub}" in self._dp_ix:
+                            tab[self._dp_ix[f"{kind}.{i}.{sub}"][0]] = t[i, j].to(torch.uint8)
+            self.dp_keep[:n * B].copy_(tab.view(-1))
+            self.dp_last = None
+        else:
+            ops.droppath_draw(self.dp_kp, self._dp_seed, self._dp_counter, self.dp_keep, B)
+            self.dp_last = (self._dp_seed, self._dp_counter)
+            self._dp_counter += 1
+
+    def _dp(self, site: Optional[str]):
+        """(the site's decisions [B], keep_prob) when the forward in flight / being differentiated drops paths at `site`, else None"""
+        if site is None or not self._dp_live or site not in self._dp_ix:
+            return None
+        j, kp = self._dp_ix[site]
+        return self.dp_keep[j * self.B:(j + 1) * self.B], kp
+
+    def _resid_lin(self, name, A, x, out, rows, dp=None):
+        """out = x + linear(A) over `rows` rows: the residual add at the end of a branch.  dp = (site, rows per sample) in the training
+        forward: at a site that drops paths the linear leaves bf16 (its bias included: the reference scales the biased branch) and
+        ego_droppath_resid adds the kept samples' branch / keep_prob"""
+        d = self._dp(dp[0]) if dp is not None else None
+        if d is None:
+            self._lin_fwd(name, A, out, rows, L.EPI_RESID, R=x)
+            return
+        self._lin_fwd(name, A, self.dp_branch, rows)
+        ops.droppath_resid(x, self.dp_branch, out, d[0], rows, dp[1], self.Dl, d[1])
+
+    def _dp_grad(self, dres_b, rows, dp):
+        """the upstream gradient of the branch at site dp = (site, rows per sample): the bf16 residual gradient itself or, where the
+        forward dropped paths, ego_droppath_scale of it (everything inside the branch is linear in it: this is the whole backward)"""
+        d = self._dp(dp[0]) if dp is not None else None
+        if d is None:
+            return dres_b
+        ops.droppath_scale(dres_b, self.dp_g, d[0], rows, dp[1], self.Dl, d[1])
+        return self.dp_g
 
     # ------------------------------------------------------------------------------------ small helpers
     def _ln(self, x, wname, y, st, out_row=None, q8=True):
@@ -849,25 +955,26 @@ class Engine:
 
     # ---- the two sub-layers every block has (Block.forward egom2p_utils.py:356-359, DecoderBlock.forward :387-391): the training
     # forward hands in each layer's saved buffers, the generation passes their shared ones
-    def _attn_sublayer(self, pre, name, x, out, rows, ln, st, qkv, ao, attn, w=None):
+    def _attn_sublayer(self, pre, name, x, out, rows, ln, st, qkv, ao, attn, w=None, dp=None):
         """out = x + proj(attention(qkv(norm1(x)))) over `rows` rows; attn(): the site's attention launch(es), qkv -> ao
-        (w: the buffers holding qkv - with qk_norm also qkn / hst, filled here: attn() then reads `_qkv_site(w)`)"""
+        (w: the buffers holding qkv - with qk_norm also qkn / hst, filled here: attn() then reads `_qkv_site(w)`; dp: the training
+        forward's rows per sample - the site may drop paths, `_resid_lin`)"""
         self._ln(x[:rows], f"{pre}.norm1.weight", ln, st)
         self._lin_fwd(f"{pre}.{name}.qkv.weight", ln, qkv, rows)
         if self.qk_norm:
             self._hn_self(pre, name, w, rows)
         attn()
-        self._lin_fwd(f"{pre}.{name}.proj.weight", ao, out, rows, L.EPI_RESID, R=x)
+        self._resid_lin(f"{pre}.{name}.proj.weight", ao, x, out, rows, dp=None if dp is None else (f"{pre}.{name}", dp))
 
-    def _mlp_sublayer(self, pre, x, out, rows, ln, st, ab, h):
+    def _mlp_sublayer(self, pre, x, out, rows, ln, st, ab, h, dp=None):
         """out = x + fc2(act(fc1(norm2(x)))) over `rows` rows"""
         self._ln(x[:rows], f"{pre}.norm2.weight", ln, st)
         self._mlp_gate_fwd(pre, ln, ab, h, rows)
-        self._lin_fwd(f"{pre}.mlp.fc2.weight", h, out, rows, L.EPI_RESID, R=x)
+        self._resid_lin(f"{pre}.mlp.fc2.weight", h, x, out, rows, dp=None if dp is None else (f"{pre}.mlp", dp))
 
     # ------------------------------------------------------------------------------------ forward
     def forward(self, mod_dict: Dict[str, Dict[str, torch.Tensor]], dec_order: Optional[Sequence[str]] = None,
-                need_loss: bool = True, group_rows: bool = True, loss_grad=None, loss_type: str = "mod"):
+                need_loss: bool = True, group_rows: bool = True, loss_grad=None, loss_type: str = "mod", training: bool = False):
         """Forward of one micro-batch (tensors already on the device).  Returns (loss, {mod: loss}) as
         views of a device buffer: reading them is the only host sync.
         loss_grad (float or 1-element device tensor, optional): the upstream d loss the following `backward` will be
@@ -875,7 +982,9 @@ class Engine:
         backward in ONE pass over the logits (`ego_ce_fwd_bwd`: bitwise the two-call result, the 16.5 GB of logits of a
         64-clip micro-batch are read once instead of twice); `backward` must then be given the same value.
         loss_type: 'mod' (forward_mod_loss, egom2p_model.py:614-644), 'weighted_mod' (:583-612) or 'token' (:646-681); the two
-        others weight the modalities' mean cross-entropies by device-side weights (`ego_loss_weights`), forward and backward."""
+        others weight the modalities' mean cross-entropies by device-side weights (`ego_loss_weights`), forward and backward.
+        training: a training-mode forward (`model.training and torch.is_grad_enabled()`): the sites of a model with drop path draw
+        their per-sample decisions and the following `backward` differentiates that forward; False (default): no path is dropped."""
         if loss_type not in ops.LOSS_MODES:
             raise ValueError("Invalid loss type")                  # the reference's message (egom2p_model.py:579)
         self._loss_mode = ops.LOSS_MODES[loss_type]
@@ -895,6 +1004,7 @@ class Engine:
         if B > self.Bmax:
             raise L.EgoHipError(f"batch {B} exceeds the engine's workspace batch {self.Bmax}")
         self.B = B
+        self._dp_begin(training, B)
         RN, RM = B * N, B * M
         byname = {m.name: m for m in mods}
         dmods = [byname[n] for n in (dec_order or [m.name for m in mods])]
@@ -932,8 +1042,8 @@ class Engine:
             nxt = self.enc[i + 1]["x"] if i + 1 < cfg.encoder_depth else self.x_enc_out
             # (key-padding mask: the per-row copies ce["ks"/"ke"] hold the same numbers as the per-sample interval)
             self._attn_sublayer(pre, "attn", w["x"], w["xm"], RN, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]), w=w)
-            self._mlp_sublayer(pre, w["xm"], nxt, RN, w["ln2"], w["st2"], w["ab"], w["h"])
+                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]), w=w, dp=N)
+            self._mlp_sublayer(pre, w["xm"], nxt, RN, w["ln2"], w["st2"], w["ab"], w["h"], dp=N)
         self._ln(self.x_enc_out[:RN], "encoder_norm.weight", self.xe, self.st_en)
         # context = decoder_proj_context(x) + encoder_emb   (egom2p_model.py:722)
         self._lin_fwd("decoder_proj_context.weight", self.xe, self.ctx, RN, L.EPI_BIAS_RESID, R=self.emb_e,
@@ -948,7 +1058,7 @@ class Engine:
             pre = f"decoder.{i}"
             nxt = self.dec[i + 1]["x"] if i + 1 < cfg.decoder_depth else self.y_out
             self._attn_sublayer(pre, "self_attn", w["x"], w["x1"], RM, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups), w=w)
+                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups), w=w, dp=M)
             self._ln(w["x1"][:RM], f"{pre}.query_norm.weight", w["qn"], w["stq"])
             self._lin_fwd(f"{pre}.cross_attn.q.weight", w["qn"], w["q"], RM)
             if not self.ctx_ln_fused:
@@ -958,8 +1068,8 @@ class Engine:
                 self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RM)
                 self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RN)
             self._attn(self._q_kv_site(w, w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
-            self._lin_fwd(f"{pre}.cross_attn.proj.weight", w["xo"], w["x2"], RM, L.EPI_RESID, R=w["x1"])
-            self._mlp_sublayer(pre, w["x2"], nxt, RM, w["ln2"], w["st2"], w["ab"], w["h"])
+            self._resid_lin(f"{pre}.cross_attn.proj.weight", w["xo"], w["x1"], w["x2"], RM, dp=(f"{pre}.cross_attn", M))
+            self._mlp_sublayer(pre, w["x2"], nxt, RM, w["ln2"], w["st2"], w["ab"], w["h"], dp=M)
         # decoder_norm, rows written modality-grouped (the row order of y[decoder_mod_mask == id], :633)
         self._ln(self.y_out[:RM], "decoder_norm.weight", self.yn, self.st_dn, out_row=self.perm if group_rows else None, q8=False)
         self._have_fwd = True
@@ -990,9 +1100,10 @@ class Engine:
         return self.loss_out[0], {m.name: self.loss_out[1 + c] for c, m in enumerate(mods)}
 
     # ------------------------------------------------------------------------------------ backward
-    def _mlp_bwd(self, pre, w, dres, dres_b, rows, xin):
-        """residual-stream gradient through x + fc2(swiglu(fc13(LN2(x)))); xin = LN2 input (saved)."""
+    def _mlp_bwd(self, pre, w, dres, dres_b, rows, xin, rps):
+        """residual-stream gradient through x + fc2(swiglu(fc13(LN2(x)))); xin = LN2 input (saved); rps: rows per sample."""
         Fp = self.Fp
+        dres_b = self._dp_grad(dres_b, rows, (f"{pre}.mlp", rps))
         dh, dab, dln = self.t_f, self.t_2f, self.t_d
         l2 = self.lin[f"{pre}.mlp.fc2.weight"]
         if self.gelu:
@@ -1013,6 +1124,7 @@ class Engine:
 
     def _self_attn_bwd(self, pre, attn_name, w, dres, dres_b, rows, Nq, mask, groups=None):
         dao, dqkv, dln = self.t_a, self.t_3d, self.t_d2
+        dres_b = self._dp_grad(dres_b, rows, (f"{pre}.{attn_name}", Nq))
         self._lin_bwd(f"{pre}.{attn_name}.proj.weight", dres_b, w["ao"], dao, rows)
         self._attn_bwd(self._qkv_site(w), w["ao"], dao, w["lse"], self._qkv_packed(dqkv), mask, self.B, Nq, Nq,
                        o_lo=w["ao_lo"], **(groups or {}))
@@ -1079,10 +1191,10 @@ class Engine:
             self.dcn = [torch.empty(self.Bmax * N, D, device=self.dev, dtype=BF16) for _ in range(cfg.decoder_depth)]
         for i in reversed(range(cfg.decoder_depth)):
             w, pre = self.dec[i], f"decoder.{i}"
-            dres_b = self._mlp_bwd(pre, w, dres, dres_b, RM, w["x2"])
+            dres_b = self._mlp_bwd(pre, w, dres, dres_b, RM, w["x2"], M)
             # cross attention
             dxo, dq, dkv, dln = self.t_a, self.t_a2, self.t_2d, self.t_d
-            self._lin_bwd(f"{pre}.cross_attn.proj.weight", dres_b, w["xo"], dxo, RM)
+            self._lin_bwd(f"{pre}.cross_attn.proj.weight", self._dp_grad(dres_b, RM, (f"{pre}.cross_attn", M)), w["xo"], dxo, RM)
             self._attn_bwd(self._q_kv_site(w, w["kv"]), w["xo"], dxo, w["lse_x"], self._q_kv(dq, dkv), enc_keys, B, M, N, o_lo=w["xo_lo"])
             if self.qk_norm:
                 self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(dq, 0, self.A), w["hstq"], RM, bwd=True)
@@ -1130,7 +1242,7 @@ class Engine:
         # ---- encoder layers
         for i in reversed(range(cfg.encoder_depth)):
             w, pre = self.enc[i], f"encoder.{i}"
-            dxe_b = self._mlp_bwd(pre, w, dxe, dxe_b, RN, w["xm"])
+            dxe_b = self._mlp_bwd(pre, w, dxe, dxe_b, RN, w["xm"], N)
             dxe_b = self._self_attn_bwd(pre, "attn", w, dxe, dxe_b, RN, N, enc_keys)
             done(pre)
         # encoder input embeddings: token rows, mod_emb (emb is used twice: x = tok + emb and context += emb)

@@ -11,6 +11,9 @@ Scope: the SwiGLU / bias-free / LayerNorm(no-bias) variant
 GELU, `qkv_bias` / `proj_bias` / `mlp_bias`, LayerNorm with bias - the `*_gelu` registrations, egom2p_model.py:881-978) with token
 modalities (`VideoToken*`, `GazeCamToken*` embeddings), with the standard or the causal decoder mask (`decoder_causal_mask`,
 always with `decoder_sep_mask=True`); `forward` takes a `mod_dict` holding any non-empty subset of the configured modalities.
+Stochastic depth (`drop_path_rate_encoder`, `drop_path_rate_decoder`, `shared_drop_path`; egom2p_model.py:96-98, 137-154) drops
+residual branches per sample in `model.train()` forwards under grad mode - decisions drawn on the device from
+`engine.set_drop_path_seed(seed, counter)` - and is inactive under `model.eval()`, `torch.no_grad()`, `return_logits` and generation.
 Other variants raise NotImplementedError.
 """
 from __future__ import annotations
@@ -147,7 +150,6 @@ class EgoM2P(nn.Module):
         if not hasattr(probe, "eps"): unsupported.append("norm_layer without eps")
         # (decoder_causal_mask=True is supported together with the modality separation: one key interval per decoder row)
         if not decoder_sep_mask: unsupported.append("decoder_sep_mask=False")
-        if drop_path_rate_encoder or drop_path_rate_decoder: unsupported.append("drop path")
         if not share_modality_embeddings: unsupported.append("unshared modality embeddings")
         if set(encoder_embeddings) != set(decoder_embeddings): unsupported.append("different encoder/decoder modality sets")
         if unsupported:
@@ -176,7 +178,8 @@ class EgoM2P(nn.Module):
                             modalities=tuple(m.name for m in mods), share_embedding=share, eps=probe.eps,
                             num_register_tokens=int(num_register_tokens), decoder_causal_mask=bool(decoder_causal_mask),
                             mlp=mlp, qkv_bias=bool(qkv_bias), proj_bias=bool(proj_bias), mlp_bias=bool(mlp_bias), norm_bias=norm_bias,
-                            qk_norm=bool(qk_norm))
+                            qk_norm=bool(qk_norm), drop_path_rate_encoder=float(drop_path_rate_encoder),
+                            drop_path_rate_decoder=float(drop_path_rate_decoder), shared_drop_path=bool(shared_drop_path))
         # ModelCfg.mods looks names up in MODALITIES: custom vocab / positions go through a private table
         self._device = device or ("cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else None)
         if self._device is None:
@@ -364,7 +367,8 @@ class EgoM2P(nn.Module):
         order = [k for k, _ in random.sample(list(md.items()), len(md))]
         if return_logits:
             return self.engine.forward_logits(md, order)
-        loss, mod_loss = self.engine.forward(md, dec_order=order, loss_type=loss_type)
+        # stochastic depth is active where the reference's DropPath is (egom2p_utils.py:93, 112: `self.training`) and a backward can follow
+        loss, mod_loss = self.engine.forward(md, dec_order=order, loss_type=loss_type, training=self.training and torch.is_grad_enabled())
         if torch.is_grad_enabled():
             loss = _LossFn.apply(self._anchor, self, loss)
         else:

@@ -320,6 +320,33 @@ def gelu_bwd(u, dh, du, rows, F, ld_u=None, ld_dh=None, ld_du=None):
                                 dh.stride(-2) if ld_dh is None else ld_dh, du.stride(-2) if ld_du is None else ld_du, _stream()), "ego_gelu_bwd")
 
 
+def droppath_draw(keep_prob, seed, counter, keep, B):
+    """keep[s, b] (uint8, a [n_sites, B] table at the front of `keep`) = the drop-path decision of site s and sample b in forward
+    `counter` of the stream `seed`: 1 iff the top 24 bits of splitmix(splitmix(splitmix(seed, counter), s), b) < floor(keep_prob[s] * 2^24)
+    (keep_prob: device fp32 [n_sites]); restated on the host in tests/_droppath_ref.py"""
+    _need_cuda(keep_prob, keep)
+    n_sites = keep_prob.numel()
+    if keep.numel() < n_sites * B:
+        raise L.EgoHipError("droppath_draw: the keep table is smaller than n_sites * B")
+    check(L.load().ego_droppath_draw(_p(keep_prob), n_sites, B, int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), _p(keep), _stream()),
+          "ego_droppath_draw")
+
+
+def droppath_resid(R, branch, out, keep, rows, rows_per_sample, width, keep_prob):
+    """out[r, :width] (f32) = R[r] + (keep[r // rows_per_sample] ? bf16(float(branch[r]) / keep_prob) : 0); out may be R; keep: the uint8
+    decisions of one site, one per sample"""
+    _need_cuda(R, branch, out, keep)
+    check(L.load().ego_droppath_resid(_p(R), R.stride(-2), _p(branch), branch.stride(-2), _p(out), out.stride(-2), _p(keep), rows,
+                                      rows_per_sample, keep.numel(), width, float(keep_prob), _stream()), "ego_droppath_resid")
+
+
+def droppath_scale(src, dst, keep, rows, rows_per_sample, width, keep_prob):
+    """dst[r, :width] (bf16) = keep[r // rows_per_sample] ? bf16(float(src[r]) / keep_prob) : 0 - a dropped branch's upstream gradient"""
+    _need_cuda(src, dst, keep)
+    check(L.load().ego_droppath_scale(_p(src), src.stride(-2), _p(dst), dst.stride(-2), _p(keep), rows, rows_per_sample, keep.numel(),
+                                      width, float(keep_prob), _stream()), "ego_droppath_scale")
+
+
 def ce_fwd(logits, ld, V, targets, rng, max_rows, lse, nll):
     check(L.load().ego_ce_fwd(_p(logits), ld, V, _p(targets), _p(rng), max_rows, _p(lse), _p(nll), _stream()), "ego_ce_fwd")
 

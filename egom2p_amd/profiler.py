@@ -175,7 +175,17 @@ class KernelTimer:
         def c_adamw(p, g, m, v, *a, zero_grad=False, **kw):
             return 0.0, float(p.numel()) * (16 + 12 + (4 if zero_grad else 0))
 
-        other = {"compact": c_compact, "embed_fwd": c_embed_fwd, "embed_bwd": c_embed_bwd, "loss_perm": c_loss_perm,
+        def c_droppath_draw(keep_prob, seed, counter, keep, B):
+            return 0.0, float(keep_prob.numel()) * (4 + B)
+
+        def c_droppath_resid(R, branch, out, keep, rows, rows_per_sample, width, keep_prob):
+            return 0.0, float(rows) * width * 10.0                      # (upper bound: a dropped sample's branch rows are not read)
+
+        def c_droppath_scale(src, dst, keep, rows, rows_per_sample, width, keep_prob):
+            return 0.0, float(rows) * width * 4.0
+
+        other = {"droppath_draw": c_droppath_draw, "droppath_resid": c_droppath_resid, "droppath_scale": c_droppath_scale,
+                 "compact": c_compact, "embed_fwd": c_embed_fwd, "embed_bwd": c_embed_bwd, "loss_perm": c_loss_perm,
                  "loss_finalize": c_loss_finalize, "cast_weight": c_cast_weight, "cast_f32_bf16": c_cast, "bias_grad": c_bias_grad,
                  "grad_sqnorm": c_sqnorm, "adamw_step": c_adamw}
         self.cost_table = dict(table, **other)

@@ -28,8 +28,9 @@ extern "C" {
  * ego_embed_desc `reg`, new ego_reg_grad - and ego_sample_cfg_topp takes top_k; 7: MaskGIT generation - new
  * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; 10: the GELU / biased
  * family - EGO_EPI_BIAS_BF16, new ego_gelu_fwd / ego_gelu_bwd, ego_layernorm_bias_fwd / ego_layernorm_bias_bwd, ego_bias_grad
- * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; loaders must refuse other versions) */
-#define EGO_ABI_VERSION 11
+ * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; 12: stochastic depth -
+ * new ego_droppath_draw / ego_droppath_resid / ego_droppath_scale; loaders must refuse other versions) */
+#define EGO_ABI_VERSION 12
 #define EGO_MAX_MODS 8
 
 /* GEMM epilogues */
@@ -208,6 +209,32 @@ int ego_headnorm_fwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H,
 long ego_headnorm_bwd_work_floats(int B, int n, int H, int n_ops);
 int ego_headnorm_bwd(const ego_headnorm_op* ops, int n_ops, int B, int n, int H, int hd, float* work, long work_floats,
                      hipStream_t stream);
+
+/* ---- stochastic depth (drop path) ---------------------------------------------------------------
+ * `drop_path` / `DropPath` (egom2p_utils.py:89-112) as the blocks apply it, x = x + drop_path(branch) (Block.forward :356-359,
+ * DecoderBlock.forward :387-391), with the per-layer rates of egom2p_model.py:137-154: one Bernoulli(keep_prob) decision per
+ * residual site and SAMPLE; a kept sample's branch is divided by keep_prob = 1 - rate, a dropped sample's branch is left out.
+ *
+ * ego_droppath_draw: the decisions of the n_sites sites of one forward, keep[s * B + b] in {0, 1} (one byte each).  keep_prob: device
+ * fp32 [n_sites].  Entry (s, b) is 1 iff the top 24 bits of splitmix(splitmix(splitmix(seed, counter), s), b) - splitmix(key, i) =
+ * the splitmix64 finaliser of key + i * 0x9E3779B97F4A7C15, the generator of ego_clip_synth - are below floor(keep_prob[s] * 2^24):
+ * integer-exact, a function of (seed, counter, s, b) alone (sample b draws the same at every batch size), no host sync. */
+int ego_droppath_draw(const float* keep_prob, int n_sites, int B, unsigned long long seed, unsigned long long counter, void* keep,
+                      hipStream_t stream);
+/* ego_droppath_resid: out[r, c] (f32) = R[r, c] (f32) + (keep[r / rows_per_sample] ? bf16(float(branch[r, c]) / keep_prob) : 0) for
+ * r < rows, c < width - the residual add of egom2p_utils.py:357-358, 388-390 behind a bf16 branch (`x.div(keep_prob) * random_tensor`,
+ * :99, under autocast).  ld_*: row pitches in elements (multiples of 8, >= width rounded up to 8); columns [width, width rounded up to
+ * 8) of out are written as zeros (padded storage keeps its pad columns zero), columns beyond are not touched.  The divide is the
+ * correctly rounded fp32 divide.  A dropped sample's rows leave as R + 0 (the reference's branch * 0)
+ * and do not read branch.  out may be R itself.  keep: the n_samples
+ * bytes of one site (a row of ego_droppath_draw's table); rows <= n_samples * rows_per_sample, 16-byte aligned pointers, 0 < keep_prob
+ * <= 1: else EGO_ERR_ARG.
+ * ego_droppath_scale: dst[r, c] (bf16) = keep[r / rows_per_sample] ? bf16(float(src[r, c]) / keep_prob) : 0 with the same indexing -
+ * the upstream gradient of the branch (the autograd of :99), applied once where the branch's backward starts. */
+int ego_droppath_resid(const float* R, long ld_r, const void* branch_bf16, long ld_b, float* out, long ld_o, const void* keep,
+                       long rows, int rows_per_sample, int n_samples, int width, float keep_prob, hipStream_t stream);
+int ego_droppath_scale(const void* src_bf16, long ld_s, void* dst_bf16, long ld_d, const void* keep, long rows, int rows_per_sample,
+                       int n_samples, int width, float keep_prob, hipStream_t stream);
 
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 inputs, fp32 MFMA accumulate.  Replaces F.linear under
  * autocast(bf16) (egom2p_utils.py:141-169, 180-203, 215-242; decoder_embeddings.py:372-383, 489-500)

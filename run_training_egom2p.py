@@ -58,6 +58,10 @@ def get_args(argv=None):
     p.add_argument("--num_register_tokens", default=0, type=int)
     p.add_argument("--qk_norm", action="store_true",
                    help="per-head LayerNorm of q and k (the *_qknorm_nobias registrations' constructor keyword; dims with heads of 64)")
+    p.add_argument("--drop_path_encoder", default=0.0, type=float,
+                   help="stochastic depth: drop rate of the last encoder layer (constructor keyword drop_path_rate_encoder; layers: linspace from 0)")
+    p.add_argument("--drop_path_decoder", default=0.0, type=float, help="the same for the decoder (drop_path_rate_decoder)")
+    p.add_argument("--shared_drop_path", action="store_true", help="one linspace of rates over encoder + decoder layers (shared_drop_path)")
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "bf16"])
     p.add_argument("--opt", default="adamw")
     p.add_argument("--opt_eps", default=1e-8, type=float)
@@ -113,7 +117,9 @@ def get_model(args):
     dec = {m: MODALITY_INFO[m]["decoder_embedding"]() for m in args.out_domains}
     return create_model(args.model, encoder_embeddings=enc, decoder_embeddings=dec,
                         modality_info={m: MODALITY_INFO[m] for m in set(args.in_domains) | set(args.out_domains)},
-                        num_register_tokens=args.num_register_tokens, **(dict(qk_norm=True) if args.qk_norm else {}))
+                        num_register_tokens=args.num_register_tokens, **(dict(qk_norm=True) if args.qk_norm else {}),
+                        **(dict(drop_path_rate_encoder=args.drop_path_encoder, drop_path_rate_decoder=args.drop_path_decoder,
+                                shared_drop_path=args.shared_drop_path) if (args.drop_path_encoder or args.drop_path_decoder) else {}))
 
 
 class SyntheticClips:
@@ -317,6 +323,9 @@ def main(args):
         # the decoder-modality shuffle draws from python's global `random` (egom2p_model.py:312): one stream per
         # (seed, epoch), so a resumed run continues with the orders an uninterrupted run would have drawn
         random.seed(seed * 1000 + epoch)
+        # the drop-path decisions are a function of (seed + rank, training forward number): the counter is set from the loader-step
+        # position, so a resumed run draws what the uninterrupted run would have drawn (evaluation forwards draw nothing)
+        model.module.engine.set_drop_path_seed(seed, counter=epoch * steps_per_epoch)
         if args.data_path:
             loader = ShardClips(args, model.module, epoch, rank, world, steps_per_epoch, seed, device)
         else:
