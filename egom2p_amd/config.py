@@ -70,6 +70,9 @@ class ModelCfg:
     drop_path_rate_encoder: float = 0.0
     drop_path_rate_decoder: float = 0.0
     shared_drop_path: bool = False
+    # activation checkpointing per block (egom2p_model.py:82): a layer saves its input, the backward rebuilds the block from it.  Owns no
+    # parameters and changes no result - only which activations stay alive between forward and backward (engine.py)
+    use_act_checkpoint: bool = False
 
     @property
     def head_dim(self) -> int:

@@ -9,7 +9,9 @@ accumulation, LayerNorm / softmax / cross-entropy / residual stream in fp32.
 Layout decisions (MI355X-first, 288 GB HBM):
   * every parameter lives in ONE flat fp32 buffer in forward order; gradients in a twin buffer, so
     gradients become final from the tail backwards and per-layer slices are the all-reduce buckets;
-  * every activation needed by the backward is kept (1.7 GB per clip at ego-b): no recompute;
+  * every activation needed by the backward is kept (1.7 GB per clip at ego-b): no recompute - unless `act_checkpoint` is set:
+    then a layer keeps only its fp32 input, every block runs in one buffer set per stack and the backward runs a block's
+    forward again in front of the block's backward (DESIGN section 4m);
   * decoder rows are written modality-grouped by the final LayerNorm so the per-modality logits / CE
     run on contiguous row ranges whose (offset, count) stay on the device (no host sync anywhere);
   * MLP hidden size is padded to a multiple of 128 in the masters themselves (pad entries are exactly
@@ -126,8 +128,11 @@ class Engine:
     pair_stream = None        # the benchmark reads and restores this around its per-kernel leg; it is always None
 
     def __init__(self, cfg: ModelCfg, device="cuda:0", max_batch: int = 1, n_enc: int = 2048, n_dec: int = 2048,
-                 attn_o_residual: str = "cross", fp8_forward: bool = False, fp8_backward: bool = False):
-        """attn_o_residual: which attention sites also keep the bf16 rounding residual of their output so that the
+                 attn_o_residual: str = "cross", fp8_forward: bool = False, fp8_backward: bool = False, act_checkpoint: bool = False):
+        """act_checkpoint (or `cfg.use_act_checkpoint`): activation checkpointing per block - every layer saves its fp32 input only, the
+        blocks of a stack run in ONE shared buffer set, and `backward` rebuilds a block from its saved input (the forward's own launches
+        on the shared set) right before the block's backward.  Same bits as the plain engine, one more pass over the blocks per step.
+        attn_o_residual: which attention sites also keep the bf16 rounding residual of their output so that the
         backward's delta = rowsum(dO o O) is formed from O to ~16 bits ("cross": the cross-attention sites - where, with
         near-uniform attention over ~2000 context keys, the plain flash-style delta put 3.5 % error on the query-path
         gradients; "all"; "none").  Costs one more bf16 [rows, D] write + read per site (~0.5 % of a step for "cross")."""
@@ -145,6 +150,7 @@ class Engine:
         if attn_o_residual not in ("cross", "all", "none"):
             raise ValueError("attn_o_residual must be 'cross', 'all' or 'none'")
         self.attn_o_residual = attn_o_residual
+        self.act_checkpoint = bool(act_checkpoint) or bool(cfg.use_act_checkpoint)     # (P, G and the layout tag do not depend on it)
         # Storage geometry.  D = the row pitch of every [rows, dim] activation and of every weight's model-dim axis: cfg.dim
         # rounded up to 128 (GEMM K steps / tiles) with zero pad columns - equal to cfg.dim for ego-b and the 1152-wide
         # ego-L; the REGISTERED ego-L (egom2p_model.py:1080-1092: dim 1020, 15 heads of 68) lives in rows of 1024.  Heads
@@ -633,8 +639,18 @@ class Engine:
                         lse_x=e(B, H, M, dt=F32), ln2=e(RM, D), ab=e(RM, self.Fab), h=e(RM, Fp), st2=e(2, RM, dt=F32),
                         **self._hn_bufs(e, self_rows=RM, q_rows=RM, k_rows=RN))
 
-        self.enc = [enc_layer() for _ in range(cfg.encoder_depth)]
-        self.dec = [dec_layer() for _ in range(cfg.decoder_depth)]
+        if self.act_checkpoint:
+            # a layer keeps its input; everything else a block writes lives once per stack (enc_sh / dec_sh: a layer's buffers without
+            # `x`) and is rebuilt from that input before the block's backward.  enc[i] / dec[i] stay the dictionaries the forward and
+            # the backward index: the layer's own x beside the stack's shared buffers.
+            self.enc_sh = {k: v for k, v in enc_layer().items() if k != "x"} if cfg.encoder_depth else {}
+            self.dec_sh = {k: v for k, v in dec_layer().items() if k != "x"} if cfg.decoder_depth else {}
+            self.enc = [dict(self.enc_sh, x=e(RN, D, dt=F32)) for _ in range(cfg.encoder_depth)]
+            self.dec = [dict(self.dec_sh, x=e(RM, D, dt=F32)) for _ in range(cfg.decoder_depth)]
+        else:
+            self.enc_sh = self.dec_sh = None
+            self.enc = [enc_layer() for _ in range(cfg.encoder_depth)]
+            self.dec = [dec_layer() for _ in range(cfg.decoder_depth)]
         self.x_enc_out = e(RN, D, dt=F32)          # residual stream after the last encoder block
         self.st_en = e(2, RN, dt=F32)
         self.xe = e(RN, D)                         # encoder_norm output (bf16)
@@ -682,6 +698,38 @@ class Engine:
             self.dp_keep = torch.ones(len(self.dp_sites) * B, device=dev, dtype=torch.uint8)     # [n_sites, B of the forward] decisions
             self.dp_branch = e(R, D)          # a site's branch: the bf16 its last linear leaves in front of ego_droppath_resid
             self.dp_g = e(R, D)               # a site's scaled upstream gradient (ego_droppath_scale of the residual gradient)
+
+    _BWD_TEMPS = ("dres", "dres_b", "ring_b", "t_d3", "dctx", "dctx_b", "dcn", "dxe", "dxe_b", "t_d", "t_d2", "t_a", "t_a2", "t_3d", "t_2d",
+                  "t_f", "t_2f", "dyn", "delta", "slab", "dp_g")
+    _FWD_OTHER = ("ce", "cd", "zero_b", "emb_e", "perm", "tgt_perm", "ranges", "perm_base", "canon", "x_enc_out", "st_en", "xe", "ctx", "y_out",
+                  "st_dn", "yn", "logits", "lse_ce", "nll", "loss_out", "loss_w", "loss_ms", "st_ctx", "q8", "qs", "gscale", "dp_kp", "dp_keep",
+                  "dp_branch")
+
+    def workspace_bytes(self) -> Dict[str, int]:
+        """Bytes of the training workspaces (`_alloc_workspaces`; `dcn` once the first backward made it), numel * element_size summed per
+        class, every buffer once: `saved` - what the layers keep for the backward, per layer (under act_checkpoint their fp32 inputs);
+        `shared` - the one block buffer set per stack of act_checkpoint (0 without); `other` - compaction, embeddings, context,
+        logits, loss; `backward` - the backward's temporaries; `total`."""
+        seen = set()
+
+        def size(o):
+            if isinstance(o, torch.Tensor):
+                if o.data_ptr() in seen:
+                    return 0
+                seen.add(o.data_ptr())
+                return o.numel() * o.element_size()
+            if isinstance(o, dict):
+                return sum(size(v) for v in o.values())
+            if isinstance(o, (list, tuple)):
+                return sum(size(v) for v in o)
+            return 0
+
+        out = dict(shared=size(self.enc_sh) + size(self.dec_sh))          # (first: a layer's dictionary names the shared buffers too)
+        out["saved"] = size(self.enc) + size(self.dec)
+        out["other"] = sum(size(getattr(self, k, None)) for k in self._FWD_OTHER)
+        out["backward"] = sum(size(getattr(self, k, None)) for k in self._BWD_TEMPS)
+        out["total"] = sum(out.values())
+        return out
 
     # ------------------------------------------------------------------------------------ stochastic depth
     def set_drop_path_seed(self, seed: int, counter: int = 0):
@@ -970,7 +1018,46 @@ class Engine:
         """out = x + fc2(act(fc1(norm2(x)))) over `rows` rows"""
         self._ln(x[:rows], f"{pre}.norm2.weight", ln, st)
         self._mlp_gate_fwd(pre, ln, ab, h, rows)
+        if out is None:           # a rebuild for the backward: the block's output is the next layer's saved input already
+            return
         self._resid_lin(f"{pre}.mlp.fc2.weight", h, x, out, rows, dp=None if dp is None else (f"{pre}.mlp", dp))
+
+    # ---- one block of the training forward over the buffers w (the layer's own or, under act_checkpoint, its x + the stack's shared
+    # set).  out = the next layer's x; None: the backward's rebuild of the block from w["x"] - the same launches on the same operands
+    # (masks, drop-path table and fp8 side buffers of the forward being differentiated) without the last residual GEMM, whose only
+    # product is `out`.  A rebuild writes w's shared buffers, dp_branch and q8 / qs: nothing the backward holds live.
+    def _enc_block(self, i, w, out):
+        pre, B, N = f"encoder.{i}", self.B, self.Ne
+        RN = B * N
+        enc_keys = _keys_per_sample(self.zero_b, self.ce["n_valid"])        # the encoder rows as keys: self- and cross-attention
+        # (key-padding mask: the per-row copies ce["ks"/"ke"] hold the same numbers as the per-sample interval)
+        self._attn_sublayer(pre, "attn", w["x"], w["xm"], RN, w["ln1"], w["st1"], w["qkv"], w["ao"],
+                            lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]), w=w, dp=N)
+        self._mlp_sublayer(pre, w["xm"], out, RN, w["ln2"], w["st2"], w["ab"], w["h"], dp=N)
+
+    def _dec_block(self, i, w, out, dec_keys, groups):
+        pre, B, N, M, cfg = f"decoder.{i}", self.B, self.Ne, self.M, self.cfg
+        RN, RM = B * N, B * M
+        enc_keys = _keys_per_sample(self.zero_b, self.ce["n_valid"])
+        self._attn_sublayer(pre, "self_attn", w["x"], w["x1"], RM, w["ln1"], w["st1"], w["qkv"], w["ao"],
+                            lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups), w=w, dp=M)
+        self._ln(w["x1"][:RM], f"{pre}.query_norm.weight", w["qn"], w["stq"])
+        self._lin_fwd(f"{pre}.cross_attn.q.weight", w["qn"], w["q"], RM)
+        if not self.ctx_ln_fused:
+            self._ln(self.ctx[:RN], f"{pre}.context_norm.weight", w["cn"], w["stc"])
+        elif self.act_checkpoint:
+            # the fused context LayerNorm would keep every layer's cn alive: under act_checkpoint the same kernel writes this layer's
+            # alone (row-local: the bits of the all-layer launch).  The forward leaves the statistics where the fused backward reads
+            # them - every layer writes the same values - a rebuild in the shared set
+            st = self.st_ctx if out is not None else w["stc"]
+            ops.layernorm_fwd_multi(self.ctx[:RN], [self.p[f"{pre}.context_norm.weight"]], [w["cn"]], st[0], st[1], eps=cfg.eps, width=self.Dl)
+        self._lin_fwd(f"{pre}.cross_attn.kv.weight", w["cn"], w["kv"], RN)
+        if self.qk_norm:
+            self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RM)
+            self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RN)
+        self._attn(self._q_kv_site(w, w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
+        self._resid_lin(f"{pre}.cross_attn.proj.weight", w["xo"], w["x1"], w["x2"], RM, dp=(f"{pre}.cross_attn", M))
+        self._mlp_sublayer(pre, w["x2"], out, RM, w["ln2"], w["st2"], w["ab"], w["h"], dp=M)
 
     # ------------------------------------------------------------------------------------ forward
     def forward(self, mod_dict: Dict[str, Dict[str, torch.Tensor]], dec_order: Optional[Sequence[str]] = None,
@@ -1036,14 +1123,8 @@ class Engine:
                       self.ranges, self.perm_base)
 
         # ---- encoder (egom2p_model.py:496-499)
-        enc_keys = _keys_per_sample(self.zero_b, ce["n_valid"])             # the encoder rows as keys: self- and cross-attention
         for i, w in enumerate(self.enc):
-            pre = f"encoder.{i}"
-            nxt = self.enc[i + 1]["x"] if i + 1 < cfg.encoder_depth else self.x_enc_out
-            # (key-padding mask: the per-row copies ce["ks"/"ke"] hold the same numbers as the per-sample interval)
-            self._attn_sublayer(pre, "attn", w["x"], w["xm"], RN, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], enc_keys, B, N, N, o_lo=w["ao_lo"]), w=w, dp=N)
-            self._mlp_sublayer(pre, w["xm"], nxt, RN, w["ln2"], w["st2"], w["ab"], w["h"], dp=N)
+            self._enc_block(i, w, self.enc[i + 1]["x"] if i + 1 < cfg.encoder_depth else self.x_enc_out)
         self._ln(self.x_enc_out[:RN], "encoder_norm.weight", self.xe, self.st_en)
         # context = decoder_proj_context(x) + encoder_emb   (egom2p_model.py:722)
         self._lin_fwd("decoder_proj_context.weight", self.xe, self.ctx, RN, L.EPI_BIAS_RESID, R=self.emb_e,
@@ -1051,25 +1132,11 @@ class Engine:
 
         # ---- decoder (egom2p_model.py:520-523)
         dec_keys, groups = _keys_per_row(cd["ks"], cd["ke"], M), self._dec_groups()
-        if self.ctx_ln_fused:
+        if self.ctx_ln_fused and not self.act_checkpoint:
             ops.layernorm_fwd_multi(self.ctx[:RN], [self.p[f"decoder.{i}.context_norm.weight"] for i in range(cfg.decoder_depth)],
                                     [w["cn"] for w in self.dec], self.st_ctx[0], self.st_ctx[1], eps=cfg.eps, width=self.Dl)
         for i, w in enumerate(self.dec):
-            pre = f"decoder.{i}"
-            nxt = self.dec[i + 1]["x"] if i + 1 < cfg.decoder_depth else self.y_out
-            self._attn_sublayer(pre, "self_attn", w["x"], w["x1"], RM, w["ln1"], w["st1"], w["qkv"], w["ao"],
-                                lambda: self._attn(self._qkv_site(w), w["ao"], w["lse"], dec_keys, B, M, M, o_lo=w["ao_lo"], **groups), w=w, dp=M)
-            self._ln(w["x1"][:RM], f"{pre}.query_norm.weight", w["qn"], w["stq"])
-            self._lin_fwd(f"{pre}.cross_attn.q.weight", w["qn"], w["q"], RM)
-            if not self.ctx_ln_fused:
-                self._ln(self.ctx[:RN], f"{pre}.context_norm.weight", w["cn"], w["stc"])
-            self._lin_fwd(f"{pre}.cross_attn.kv.weight", w["cn"], w["kv"], RN)
-            if self.qk_norm:
-                self._hn_one(f"{pre}.cross_attn.q_norm.weight", _Rows(w["q"], 0, self.A), _Rows(w["xqn"], 0, self.A), w["hstq"], RM)
-                self._hn_one(f"{pre}.cross_attn.k_norm.weight", _Rows(w["kv"], 0, 2 * self.A), _Rows(w["xkn"], 0, 2 * self.A), w["hstk"], RN)
-            self._attn(self._q_kv_site(w, w["kv"]), w["xo"], w["lse_x"], enc_keys, B, M, N, o_lo=w["xo_lo"])
-            self._resid_lin(f"{pre}.cross_attn.proj.weight", w["xo"], w["x1"], w["x2"], RM, dp=(f"{pre}.cross_attn", M))
-            self._mlp_sublayer(pre, w["x2"], nxt, RM, w["ln2"], w["st2"], w["ab"], w["h"], dp=M)
+            self._dec_block(i, w, self.dec[i + 1]["x"] if i + 1 < cfg.decoder_depth else self.y_out, dec_keys, groups)
         # decoder_norm, rows written modality-grouped (the row order of y[decoder_mod_mask == id], :633)
         self._ln(self.y_out[:RM], "decoder_norm.weight", self.yn, self.st_dn, out_row=self.perm if group_rows else None, q8=False)
         self._have_fwd = True
@@ -1191,6 +1258,8 @@ class Engine:
             self.dcn = [torch.empty(self.Bmax * N, D, device=self.dev, dtype=BF16) for _ in range(cfg.decoder_depth)]
         for i in reversed(range(cfg.decoder_depth)):
             w, pre = self.dec[i], f"decoder.{i}"
+            if self.act_checkpoint and i + 1 < cfg.decoder_depth:      # (the forward left the stack's last block in the shared set)
+                self._dec_block(i, w, None, dec_keys, groups)
             dres_b = self._mlp_bwd(pre, w, dres, dres_b, RM, w["x2"], M)
             # cross attention
             dxo, dq, dkv, dln = self.t_a, self.t_a2, self.t_2d, self.t_d
@@ -1242,6 +1311,8 @@ class Engine:
         # ---- encoder layers
         for i in reversed(range(cfg.encoder_depth)):
             w, pre = self.enc[i], f"encoder.{i}"
+            if self.act_checkpoint and i + 1 < cfg.encoder_depth:
+                self._enc_block(i, w, None)
             dxe_b = self._mlp_bwd(pre, w, dxe, dxe_b, RN, w["xm"], N)
             dxe_b = self._self_attn_bwd(pre, "attn", w, dxe, dxe_b, RN, N, enc_keys)
             done(pre)

@@ -14,6 +14,8 @@ always with `decoder_sep_mask=True`); `forward` takes a `mod_dict` holding any n
 Stochastic depth (`drop_path_rate_encoder`, `drop_path_rate_decoder`, `shared_drop_path`; egom2p_model.py:96-98, 137-154) drops
 residual branches per sample in `model.train()` forwards under grad mode - decisions drawn on the device from
 `engine.set_drop_path_seed(seed, counter)` - and is inactive under `model.eval()`, `torch.no_grad()`, `return_logits` and generation.
+`use_act_checkpoint=True` (egom2p_model.py:82) builds a checkpointing engine: every block keeps its input only and is run again in
+front of its backward - the same losses, gradients and updates bit for bit, a fraction of the activation memory, one more pass over the blocks.
 Other variants raise NotImplementedError.
 """
 from __future__ import annotations
@@ -179,7 +181,8 @@ class EgoM2P(nn.Module):
                             num_register_tokens=int(num_register_tokens), decoder_causal_mask=bool(decoder_causal_mask),
                             mlp=mlp, qkv_bias=bool(qkv_bias), proj_bias=bool(proj_bias), mlp_bias=bool(mlp_bias), norm_bias=norm_bias,
                             qk_norm=bool(qk_norm), drop_path_rate_encoder=float(drop_path_rate_encoder),
-                            drop_path_rate_decoder=float(drop_path_rate_decoder), shared_drop_path=bool(shared_drop_path))
+                            drop_path_rate_decoder=float(drop_path_rate_decoder), shared_drop_path=bool(shared_drop_path),
+                            use_act_checkpoint=bool(use_act_checkpoint))
         # ModelCfg.mods looks names up in MODALITIES: custom vocab / positions go through a private table
         self._device = device or ("cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else None)
         if self._device is None:

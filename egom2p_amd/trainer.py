@@ -24,7 +24,8 @@ class TrainStep:
         """clips_per_step (per rank) bounds the table rows one step can touch (clips x kept encoder tokens); with
         sparse_tables = "auto" the encoder tables' gradients go through the row-list exchange when that moves fewer bytes
         than the dense all-reduce ("on" / "off" force it).  dp_algo: "allreduce" | "rs_ag" (GradBucketReducer); dp_backend:
-        "torch" (torch.distributed's RCCL) or "cabi" (the library's own communicator, ego_dp_*; GPU groups only)."""
+        "torch" (torch.distributed's RCCL) or "cabi" (the library's own communicator, ego_dp_*; GPU groups only).
+        Activation checkpointing is the engine's own setting (`Engine(act_checkpoint=True)`): the step drives either engine alike."""
         self.engine = engine
         self.opt = FusedAdamW(engine, lr=lr, weight_decay=weight_decay, world_size=world_size)
         self.clip = clip_grad

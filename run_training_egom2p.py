@@ -62,6 +62,9 @@ def get_args(argv=None):
                    help="stochastic depth: drop rate of the last encoder layer (constructor keyword drop_path_rate_encoder; layers: linspace from 0)")
     p.add_argument("--drop_path_decoder", default=0.0, type=float, help="the same for the decoder (drop_path_rate_decoder)")
     p.add_argument("--shared_drop_path", action="store_true", help="one linspace of rates over encoder + decoder layers (shared_drop_path)")
+    p.add_argument("--act_checkpoint", action="store_true",
+                   help="activation checkpointing per block (constructor keyword use_act_checkpoint): a layer keeps its input only and the "
+                        "backward runs the block again - the same results bit for bit, less activation memory, more time per step")
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "bf16"])
     p.add_argument("--opt", default="adamw")
     p.add_argument("--opt_eps", default=1e-8, type=float)
@@ -118,6 +121,7 @@ def get_model(args):
     return create_model(args.model, encoder_embeddings=enc, decoder_embeddings=dec,
                         modality_info={m: MODALITY_INFO[m] for m in set(args.in_domains) | set(args.out_domains)},
                         num_register_tokens=args.num_register_tokens, **(dict(qk_norm=True) if args.qk_norm else {}),
+                        **(dict(use_act_checkpoint=True) if args.act_checkpoint else {}),
                         **(dict(drop_path_rate_encoder=args.drop_path_encoder, drop_path_rate_decoder=args.drop_path_decoder,
                                 shared_drop_path=args.shared_drop_path) if (args.drop_path_encoder or args.drop_path_decoder) else {}))
 
