@@ -799,7 +799,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_kernel(NTArgs p) {
                         for (int t = 0; t < 2; ++t) {
                             const float sg = sigmoidf_(a2[t]);
                             da[t] = g2[t] * b2[t] * sg * (1.f + a2[t] * (1.f - sg));
-                            db[t] = g2[t] * a2[t] * sg;
+                            db[t] = g2[t] * (a2[t] * sg);      // silu first, like swiglu_bwd_kernel: dh * a leaves fp32 where silu(a) is 0
                         }
                         oa[e] = pack_bf16x2(da[0], da[1]);
                         ob[e] = pack_bf16x2(db[0], db[1]);

@@ -516,7 +516,7 @@ __global__ void swiglu_bwd_kernel(const bf16_t* __restrict__ ab, const bf16_t* _
             for (int k = 0; k < 2; ++k) {
                 const float s = sigmoidf_(av[k]);
                 da[k] = gv[k] * bv[k] * s * (1.f + av[k] * (1.f - s));
-                db[k] = gv[k] * av[k] * s;
+                db[k] = gv[k] * (av[k] * s);           // silu(a) first: dh * a overflows for |a| near the end of bf16's range, and inf * 0 is NaN
             }
             oa[e] = pack_bf16x2(da[0], da[1]);
             ob[e] = pack_bf16x2(db[0], db[1]);
