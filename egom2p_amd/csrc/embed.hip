@@ -783,6 +783,10 @@ extern "C" long ego_embed_bwd_work_floats(long rows, int D, int n_mods) {
 extern "C" int ego_embed_bwd(const ego_embed_bwd_desc* d, hipStream_t stream) {
     if (!d || d->rows <= 0 || d->D % 4 || d->D > 2048 || d->n_mods <= 0 || d->n_mods > EGO_MAX_MODS || d->rows > 0x7fffffffL) return EGO_ERR_ARG;
     if (!d->work || d->work_floats < ego_embed_bwd_work_floats(d->rows, d->D, d->n_mods)) return EGO_ERR_ARG;
+    // table ids index 16-bit key fields: vocabularies up to 65536 (the reference's largest is 64000); a larger id would
+    // alias another row's key: `vocab` (optional, 0 = not given) lets the caller have that checked here - before the first
+    // launch, so that a refused call has added nothing to dmod / dbase
+    for (int m = 0; m < d->n_mods; ++m) if (d->dtable[m] && d->vocab[m] > 65536) return EGO_ERR_ARG;
     EmbedBwdArgs a{};
     bool tables = false;
     for (int m = 0; m < EGO_MAX_MODS; ++m) { a.dtable[m] = d->dtable[m]; a.dmod[m] = d->dmod[m]; tables |= d->dtable[m] != nullptr; }
@@ -808,9 +812,6 @@ extern "C" int ego_embed_bwd(const ego_embed_bwd_desc* d, hipStream_t stream) {
     colsum_launch(d->work, nwg, W, dst, stream);
     LAUNCH_CHECK();
     if (tables) {
-        // table ids index 16-bit key fields: vocabularies up to 65536 (the reference's largest is 64000); a larger id would
-        // alias another row's key: `vocab` (optional, 0 = not given) lets the caller have that checked here
-        for (int m = 0; m < d->n_mods; ++m) if (d->dtable[m] && d->vocab[m] > 65536) return EGO_ERR_ARG;
         const size_t lds2 = (size_t)(5 * ET_CAP + 8) * sizeof(int) + (size_t)4 * d->D * sizeof(float);
 #define ET_GO(C) do { if (hipFuncSetAttribute((const void*)embed_tables_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) \
                           return EGO_ERR_LAUNCH;                                                                                        \
