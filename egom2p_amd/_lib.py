@@ -67,6 +67,7 @@ _SIGS = {
     "ego_attn_tune": [i32, i32],
     "ego_compact": [C.POINTER(CompactDesc), i32, vp],
     "ego_compact_causal": [C.POINTER(CompactDesc), i32, vp],
+    "ego_compact_nosep": [C.POINTER(CompactDesc), i32, i32, vp],
     "ego_embed_fwd": [C.POINTER(EmbedDesc), vp],
     "ego_embed_bwd_work_floats": [i64, i32, i32],
     "ego_embed_bwd": [C.POINTER(EmbedBwdDesc), vp],

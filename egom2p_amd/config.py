@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import hashlib
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 
 def uint15_hash(name: str) -> int:
@@ -73,6 +73,14 @@ class ModelCfg:
     # activation checkpointing per block (egom2p_model.py:82): a layer saves its input, the backward rebuilds the block from it.  Owns no
     # parameters and changes no result - only which activations stay alive between forward and backward (engine.py)
     use_act_checkpoint: bool = False
+    # asymmetric models (run_training_egom2p.py:354-389: encoder_embeddings from --in_domains, decoder_embeddings from --out_domains):
+    # the modalities with an encoder / a decoder embedding, each a subset of `modalities`; None: all of them
+    encoder_modalities: Optional[Tuple[str, ...]] = None
+    decoder_modalities: Optional[Tuple[str, ...]] = None
+    # decoder mod_emb tied to the encoder's where a modality has both (share_modality_embeddings(), egom2p_model.py:179-183)
+    share_modality_embeddings: bool = True
+    # the modality separation of the decoder's self-attention mask (adapt_decoder_attention_mask, egom2p_model.py:476-479)
+    decoder_sep_mask: bool = True
 
     @property
     def head_dim(self) -> int:
@@ -88,6 +96,24 @@ class ModelCfg:
     @property
     def mods(self) -> List[Modality]:
         return [MODALITIES[m] for m in self.modalities]
+
+    def _side(self, names) -> List[Modality]:
+        if names is None:
+            return self.mods
+        unknown = [n for n in names if n not in self.modalities]
+        if unknown:
+            raise ValueError(f"{unknown} not among the model's modalities {self.modalities}")
+        return [MODALITIES[m] for m in self.modalities if m in names]
+
+    @property
+    def enc_mods(self) -> List[Modality]:
+        """the modalities with an encoder embedding, in `modalities` order"""
+        return self._side(self.encoder_modalities)
+
+    @property
+    def dec_mods(self) -> List[Modality]:
+        """the modalities with a decoder embedding, in `modalities` order"""
+        return self._side(self.decoder_modalities)
 
     @property
     def total_positions(self) -> int:

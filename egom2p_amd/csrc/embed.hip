@@ -22,6 +22,7 @@ struct CompactArgs {
     int n_mods, T, n_keep, is_decoder;
     int n_reg;                // register rows in front of every sample's kept rows (encoder only): outputs are [B, n_reg + n_keep]
     int causal;               // decoder only: decoder_causal_mask (egom2p_model.py:459-463) - the cumsum rule gives way to triu(1)
+    int nosep;                // decoder only: decoder_sep_mask=False - no modality separation (egom2p_model.py:476-479 left out)
     long long* ids_keep;      // [B, n_keep]
     unsigned char* pad;       // [B, n_keep]
     short* mod_mask;          // [B, n_keep]  (-1 on pads)
@@ -178,7 +179,18 @@ __global__ __launch_bounds__(256) void compact_kernel(CompactArgs a) {
 #pragma unroll
                     for (int k = 0; k < EGO_MAX_MODS; ++k) if (k == m) { sa = segstart[k]; sb = segstart[k + 1]; }
                     const int s0 = min(sa, a.n_keep), s1 = min(sb, a.n_keep);
-                    if (a.causal) {
+                    if (a.nosep) {
+                        // decoder_sep_mask=False: adapt_decoder_attention_mask without its separation term (egom2p_model.py:
+                        // 476-479) - key j is visible iff j < cumsum(dam)_i, or j <= i under triu(1): one interval from key 0,
+                        // across the modalities' segments.  The "visible pad key" rule is the cumsum mode's own (a causal row
+                        // sees no index above its own); pad rows get every valid key, as in the other modes.
+                        const int e = a.causal ? out + 1 : min(cs, a.n_keep);
+                        a.ks[o] = 0;
+                        a.ke[o] = unm ? e : nv;
+                        if (!a.causal && cs > nv && nv < a.n_keep) atomicOr(a.err, 1);
+                        // a row group stands for "every row sees exactly its slot's segment": anything else takes the per-row path
+                        if (unm && a.seg_bad && (s0 != 0 || e != s1)) atomicOr(a.seg_bad + b, 1);
+                    } else if (a.causal) {
                         // decoder_causal_mask: triu(1) | (mod_mask differs) (egom2p_model.py:459-463, 476-479; the
                         // decoder_attention_mask is not read).  The kept rows of a modality are contiguous, so kept row `out`
                         // of segment [s0, s1) sees exactly the keys [s0, out + 1).  Every pad key has an index >= nv > out:
@@ -694,11 +706,12 @@ extern "C" int ego_rows_scatter(float* table, const int* rows, const int* count,
     return EGO_OK;
 }
 
-static int compact_launch(const ego_compact_desc* d, int B, int causal, hipStream_t stream) {
+static int compact_launch(const ego_compact_desc* d, int B, int causal, int nosep, hipStream_t stream) {
     if (!d || d->n_mods <= 0 || d->n_mods > EGO_MAX_MODS || B <= 0) return EGO_ERR_ARG;
-    if (causal && !d->is_decoder) return EGO_ERR_ARG;
+    if ((causal || nosep) && !d->is_decoder) return EGO_ERR_ARG;
     CompactArgs a{};
     a.causal = causal;
+    a.nosep = nosep;
     int T = 0;
     for (int m = 0; m < d->n_mods; ++m) {
         a.mask[m] = (const unsigned char*)d->mask[m];
@@ -721,9 +734,13 @@ static int compact_launch(const ego_compact_desc* d, int B, int causal, hipStrea
     return EGO_OK;
 }
 
-extern "C" int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 0, stream); }
+extern "C" int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 0, 0, stream); }
 
-extern "C" int ego_compact_causal(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 1, stream); }
+extern "C" int ego_compact_causal(const ego_compact_desc* d, int B, hipStream_t stream) { return compact_launch(d, B, 1, 0, stream); }
+
+extern "C" int ego_compact_nosep(const ego_compact_desc* d, int B, int causal, hipStream_t stream) {
+    return compact_launch(d, B, causal ? 1 : 0, 1, stream);
+}
 
 extern "C" int ego_embed_fwd(const ego_embed_desc* d, hipStream_t stream) {
     if (!d || d->rows <= 0 || d->D % 4) return EGO_ERR_ARG;

@@ -208,8 +208,20 @@ class Engine:
         self._dp_live = False                 # the forward in flight / being differentiated drops paths
         self._dp_seed, self._dp_counter, self._dp_inject = 0, 0, None
         self.dp_last = None                   # (seed, forward counter) the last training forward drew with; None: injected tables
-        self.mods: List[Modality] = cfg.mods
+        # asymmetric models (run_training_egom2p.py:354-389): enc_mods own an encoder embedding, dec_mods a decoder embedding; mods =
+        # the ones in either set, in configuration order (slots, positional tables, workspace sizes).  A symmetric model: all three equal.
+        self.enc_mods: List[Modality] = cfg.enc_mods
+        self.dec_mods: List[Modality] = cfg.dec_mods
+        if not self.enc_mods or not self.dec_mods:
+            raise ValueError("a model needs at least one encoder and one decoder modality")
+        either = {m.name for m in self.enc_mods} | {m.name for m in self.dec_mods}
+        self.mods: List[Modality] = [m for m in cfg.mods if m.name in either]
         self.n_mods = len(self.mods)
+        # decoder modalities whose mod_emb is a parameter of its own: the decoder-only ones and, with share_modality_embeddings=False,
+        # all of them; the others alias the encoder's (share_modality_embeddings(), egom2p_model.py:179-183: the intersection)
+        enc_names = {m.name for m in self.enc_mods}
+        self.dec_own_mod_emb = {m.name for m in self.dec_mods if not cfg.share_modality_embeddings or m.name not in enc_names}
+        self.sep_mask = bool(cfg.decoder_sep_mask)
         self.N, self.M, self.Bmax = n_enc, n_dec, max_batch
         # register tokens (egom2p_model.py:170-171, 381-387): R learned rows in front of every sample's N kept encoder tokens - the
         # encoder, the context and the cross-attention keys have Ne = R + N rows per sample; the compaction keeps N
@@ -221,7 +233,7 @@ class Engine:
         self._alloc_workspaces()
         self.weights_dirty = True
         self._have_fwd = False
-        self.fmods = self.mods                          # the modalities of the last forward (a mod_dict may hold a subset)
+        self.fmods, self.femods = self.dec_mods, self.enc_mods      # the decoder / encoder modalities of the last forward (a mod_dict may hold a subset)
         self._ce_done, self._ce_grad = set(), None      # modalities whose CE backward ran inside the forward (loss_grad)
         self._loss_mode = 0                             # ops.LOSS_MODES of the last forward
         self._canon_dev = {}                            # decoder order -> its modality indices on the device
@@ -299,11 +311,11 @@ class Engine:
             add(f"{prefix}.mlp.fc2.weight", (D, Fp))
 
         marks = []
-        for m in self.mods:
+        for m in self.enc_mods:
             marks.append((f"enc_table.{m.name}", len(spec)))
             add(f"encoder_embeddings.{m.name}.token_emb.weight", (m.vocab_size, D))
         marks.append(("mod_emb", len(spec)))
-        for m in self.mods:
+        for m in self.enc_mods:
             add(f"encoder_embeddings.{m.name}.mod_emb", (D,))
         if cfg.num_register_tokens:
             add("register_tokens", (cfg.num_register_tokens, D))       # reference shape (1, R, dim); decayed like mod_emb / mask_token
@@ -324,11 +336,16 @@ class Engine:
         marks.append(("head", len(spec)))
         norm("decoder_norm")
         add("mask_token", (D,))
-        for m in self.mods:
+        # a decoder modality's own mod_emb (decoder-only modalities; all of them when unshared) sits beside the mask token: decayed
+        # like it, final with it (the decoder embedding backward), in the "head" bucket.  A symmetric shared model has none.
+        for m in self.dec_mods:
+            if m.name in self.dec_own_mod_emb:
+                add(f"decoder_embeddings.{m.name}.mod_emb", (D,))
+        for m in self.dec_mods:
             marks.append((f"dec_table.{m.name}", len(spec)))
             add(f"decoder_embeddings.{m.name}.token_emb.weight", (m.vocab_size, D))
         if not cfg.share_embedding:
-            for m in self.mods:
+            for m in self.dec_mods:
                 marks.append((f"to_logits.{m.name}", len(spec)))
                 add(f"decoder_embeddings.{m.name}.to_logits.weight", (m.vocab_size, D))
 
@@ -351,7 +368,7 @@ class Engine:
         # optimiser runs: contiguous ranges of equal weight-decay class (no_decay: norm weights and biases)
         # tensors no kernel ever writes a gradient for: with an untied head the decoder token tables are never read (the
         # decoder rows are the mask token, egom2p_model.py:328), the reference leaves their .grad None and AdamW skips them
-        self.never_grad = set() if cfg.share_embedding else {f"decoder_embeddings.{m.name}.token_emb.weight" for m in self.mods}
+        self.never_grad = set() if cfg.share_embedding else {f"decoder_embeddings.{m.name}.token_emb.weight" for m in self.dec_mods}
         runs: List[List] = []
         for name, shape in spec:
             if name in self.never_grad:
@@ -391,7 +408,10 @@ class Engine:
             lin(f"decoder.{i}.mlp.fc1.weight") if self.gelu else self._fuse13(f"decoder.{i}")
         lin("decoder_proj_context.weight")
         self.logit_key = {m.name: (f"decoder_embeddings.{m.name}.token_emb.weight" if cfg.share_embedding
-                                   else f"decoder_embeddings.{m.name}.to_logits.weight") for m in self.mods}
+                                   else f"decoder_embeddings.{m.name}.to_logits.weight") for m in self.dec_mods}
+        # the mod_emb a decoder row of modality m adds: its own parameter, or the encoder's
+        self.dec_mod_emb_key = {m.name: (f"decoder_embeddings.{m.name}.mod_emb" if m.name in self.dec_own_mod_emb
+                                         else f"encoder_embeddings.{m.name}.mod_emb") for m in self.dec_mods}
         for key in self.logit_key.values():
             lin(key)
 
@@ -458,7 +478,10 @@ class Engine:
         for key, val in sd.items():
             if self._is_buffer_key(key):
                 continue
-            if self._canon_key(key) not in self.p:
+            side = key.split(".")
+            foreign = ((side[0] == "decoder_embeddings" and side[1] not in self.logit_key) or
+                       (side[0] == "encoder_embeddings" and f"encoder_embeddings.{side[1]}.mod_emb" not in self.p))
+            if foreign or self._canon_key(key) not in self.p:           # (an embedding of the side this model has none on: no alias)
                 unexpected.append(key)
                 continue
             v = self._view_for_key(key)
@@ -473,15 +496,19 @@ class Engine:
         def ref(name):           # the reference's tensor: a view of the storage, or (padded layouts) a copy without the pads
             return self._view_for_key(name).reshape(self._ref_shape(name))
 
+        enc_names, dec_names = {m.name for m in self.enc_mods}, {m.name for m in self.dec_mods}
         for m in self.mods:
             e, d = f"encoder_embeddings.{m.name}", f"decoder_embeddings.{m.name}"
-            out[f"{e}.mod_emb"] = ref(f"{e}.mod_emb").view(1, 1, D)
-            out[f"{e}.token_emb.weight"] = ref(f"{e}.token_emb.weight")
-            out[f"{e}.pos_emb"] = self.pos[m.name][None, :, :D]
-            out[f"{d}.mod_emb"] = out[f"{e}.mod_emb"]
-            out[f"{d}.token_emb.weight"] = ref(f"{d}.token_emb.weight")
-            out[f"{d}.to_logits.weight"] = ref(self.logit_key[m.name])
-            out[f"{d}.pos_emb"] = self.pos[m.name][None, :, :D]
+            if m.name in enc_names:
+                out[f"{e}.mod_emb"] = ref(f"{e}.mod_emb").view(1, 1, D)
+                out[f"{e}.token_emb.weight"] = ref(f"{e}.token_emb.weight")
+                out[f"{e}.pos_emb"] = self.pos[m.name][None, :, :D]
+            if m.name in dec_names:
+                own = m.name in self.dec_own_mod_emb
+                out[f"{d}.mod_emb"] = ref(f"{d}.mod_emb").view(1, 1, D) if own else out[f"{e}.mod_emb"]
+                out[f"{d}.token_emb.weight"] = ref(f"{d}.token_emb.weight")
+                out[f"{d}.to_logits.weight"] = ref(self.logit_key[m.name])
+                out[f"{d}.pos_emb"] = self.pos[m.name][None, :, :D]
         zeros = torch.zeros(D, device=self.dev)
         for name in self.p:
             if name.startswith(("encoder.", "decoder.", "encoder_norm", "decoder_norm", "decoder_proj_context")):
@@ -495,7 +522,7 @@ class Engine:
 
     def _canon_key(self, key: str) -> str:
         """reference state-dict key -> engine storage key (shared mod_emb, tied to_logits)."""
-        if key.startswith("decoder_embeddings") and key.endswith("mod_emb"):
+        if key.startswith("decoder_embeddings") and key.endswith("mod_emb") and key.split(".")[1] not in self.dec_own_mod_emb:
             key = key.replace("decoder_embeddings", "encoder_embeddings")
         if key.endswith("to_logits.weight") and self.cfg.share_embedding:
             key = key.replace("to_logits.weight", "token_emb.weight")
@@ -986,7 +1013,7 @@ class Engine:
         """Row groups of the decoder's block-diagonal self-attention mask for the attention kernels (head dim 64): the
         compaction's (start, count) per modality slot + its per-sample "not the contract's mask" flags.  With them every
         attention workgroup sees one interval; EGOM2P_ATTN_GROUPS=0 keeps the per-row launches."""
-        if self.HDP != 64 or not self.attn_groups:
+        if self.HDP != 64 or not self.attn_groups or not self.sep_mask:      # (no separation: a row's keys are no modality segment)
             return {}
         # (the compaction packs (start, count) per PRESENT modality slot: [B, len(present), 2] at the front of the buffer.  A causal
         #  decoder goes through the same launch: ego_compact_causal raises seg_bad for every sample whose groups are not single rows,
@@ -1083,10 +1110,14 @@ class Engine:
         unknown = [k for k in mod_dict if k not in {m.name for m in self.mods}]
         if unknown:
             raise KeyError(f"not a configured modality: {unknown}")
-        mods = [m for m in self.mods if m.name in mod_dict]
-        if not mods:
-            raise ValueError("mod_dict holds no modality")
-        self.fmods, n_mods = mods, len(mods)
+        # the encoder takes the entries that are encoder modalities, the decoder (and the loss) those that are decoder modalities
+        # (egom2p_model.py:706-714: each side walks the mod_dict keys it has an embedding for); a symmetric model: one list
+        emods = [m for m in self.enc_mods if m.name in mod_dict]
+        mods = [m for m in self.dec_mods if m.name in mod_dict]
+        if not emods or not mods:
+            raise ValueError("mod_dict holds no modality" if not (emods or mods) else
+                             "mod_dict holds no encoder modality" if not emods else "mod_dict holds no decoder modality")
+        self.fmods, self.femods, n_mods = mods, emods, len(mods)
         B = mod_dict[mods[0].name]["input_mask"].shape[0]
         if B > self.Bmax:
             raise L.EgoHipError(f"batch {B} exceeds the engine's workspace batch {self.Bmax}")
@@ -1094,7 +1125,7 @@ class Engine:
         self._dp_begin(training, B)
         RN, RM = B * N, B * M
         byname = {m.name: m for m in mods}
-        dmods = [byname[n] for n in (dec_order or [m.name for m in mods])]
+        dmods = [byname[n] for n in (dec_order or [m.name for m in mods])]      # (dec_order names decoder modalities of the batch)
         self.dmods = dmods
 
         def flat_ids(m):
@@ -1103,17 +1134,18 @@ class Engine:
 
         # ---- compaction + embeddings (egom2p_model.py:706-718, 723)
         ce, cd = self.ce, self.cd
-        ops.compact([mod_dict[m.name]["input_mask"] for m in mods], [flat_ids(m) for m in mods], None,
-                    [m.max_tokens for m in mods], [m.id for m in mods], self.N, False, ce, B, n_reg=self.R)
+        ops.compact([mod_dict[m.name]["input_mask"] for m in emods], [flat_ids(m) for m in emods], None,
+                    [m.max_tokens for m in emods], [m.id for m in emods], self.N, False, ce, B, n_reg=self.R)
         ops.compact([mod_dict[m.name]["target_mask"] for m in dmods], [flat_ids(m) for m in dmods],
                     [mod_dict[m.name]["decoder_attention_mask"] for m in dmods],
-                    [m.max_tokens for m in dmods], [m.id for m in dmods], M, True, cd, B, causal=bool(cfg.decoder_causal_mask))
+                    [m.max_tokens for m in dmods], [m.id for m in dmods], M, True, cd, B, causal=bool(cfg.decoder_causal_mask),
+                    sep=self.sep_mask)
         x0 = self.enc[0]["x"] if cfg.encoder_depth else self.x_enc_out
-        ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
-                      [self.pos[m.name] for m in mods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods],
+        ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in emods],
+                      [self.pos[m.name] for m in emods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in emods],
                       None, ce["slot"], ce["local"], ce["tok"], x0, self.emb_e, RN, D, reg=self.p["register_tokens"] if self.R else None)
         y0 = self.dec[0]["x"] if cfg.decoder_depth else self.y_out
-        ops.embed_fwd(None, [self.pos[m.name] for m in dmods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in dmods],
+        ops.embed_fwd(None, [self.pos[m.name] for m in dmods], [self.p[self.dec_mod_emb_key[m.name]] for m in dmods],
                       self.p["mask_token"], cd["slot"], cd["local"], cd["tok"], y0, None, RM, D)
         ckey = tuple(m.name for m in dmods)
         if ckey not in self._canon_dev:              # one small H2D copy per decoder order, ever (never inside a graph capture)
@@ -1215,7 +1247,7 @@ class Engine:
         assert self._have_fwd, "backward() needs a forward()"
         cfg, D, N, M, B = self.cfg, self.D, self.Ne, self.M, self.B       # N: encoder rows per sample (registers included)
         RN, RM = B * N, B * M
-        mods, ce, cd = self.fmods, self.ce, self.cd           # the modalities of the forward (absent ones: no kernel writes their gradients)
+        mods, emods, ce, cd = self.fmods, self.femods, self.ce, self.cd     # the decoder / encoder modalities of the forward (absent ones: no kernel writes their gradients)
         if self._ce_done:
             # the forward already turned the logits into d logits with the upstream gradient it was promised
             same = (gscale is self._ce_grad) or (not isinstance(gscale, torch.Tensor) and not isinstance(self._ce_grad, torch.Tensor)
@@ -1243,7 +1275,7 @@ class Engine:
                            loss_w=self.loss_w[c:c + 1] if self._loss_mode else None)
             ops.gemm_nt(lg, l.wt, self.dyn, ub, D, V, L.EPI_BF16, m_range=self.ranges[c], lda=V, ldb=V, ldc=D)
             self._wgrad(l.g, lg, self.yn, V, D, ub, ldp=V, ldq=D, m_range=self.ranges[c])
-        for m in reversed(self.mods):                          # (every bucket is handed over, an absent modality's with zeros)
+        for m in reversed(self.dec_mods):                      # (every bucket is handed over, an absent modality's with zeros)
             done(f"dec_table.{m.name}" if cfg.share_embedding else f"to_logits.{m.name}")
         dres, dres_b = self.dres, self._ring_next()
         ops.layernorm_bwd(self.dyn, self.y_out[:RM], self.st_dn[0], self.st_dn[1], self.p["decoder_norm.weight"], dres,
@@ -1294,7 +1326,7 @@ class Engine:
             done("ctx_norms")
         # decoder input embeddings: mask token + (pos + mod_emb)
         dmods = self.dmods
-        ops.embed_bwd(None, [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in dmods], self.g["mask_token"],
+        ops.embed_bwd(None, [self.g[self.dec_mod_emb_key[m.name]] for m in dmods], self.g["mask_token"],
                       dres, None, cd["slot"], cd["tok"], RM, D)
         done("head")
 
@@ -1317,14 +1349,14 @@ class Engine:
             dxe_b = self._self_attn_bwd(pre, "attn", w, dxe, dxe_b, RN, N, enc_keys)
             done(pre)
         # encoder input embeddings: token rows, mod_emb (emb is used twice: x = tok + emb and context += emb)
-        ops.embed_bwd([self.g[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods],
-                      [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, dxe, self.dctx,
+        ops.embed_bwd([self.g[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in emods],
+                      [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in emods], None, dxe, self.dctx,
                       ce["slot"], ce["tok"], RN, D,
-                      touched=None if self.touched is None else [self.touched[self.mods.index(m)] for m in mods])
+                      touched=None if self.touched is None else [self.touched[self.enc_mods.index(m)] for m in emods])
         if self.R:        # d register_tokens = the encoder input gradient of the register rows, summed over the batch (emb is 0 there)
             ops.reg_grad(dxe, B, N, self.R, D, self.g["register_tokens"])
         done("mod_emb")
-        for m in reversed(self.mods):
+        for m in reversed(self.enc_mods):
             done(f"enc_table.{m.name}")
         self._have_fwd = False
         self._ce_done = set()
@@ -1339,8 +1371,8 @@ class Engine:
         if not on:
             self.touched = None
             return []
-        self.touched = [torch.zeros(m.vocab_size, device=self.dev, dtype=torch.uint8) for m in self.mods]
-        return [(self.g[f"encoder_embeddings.{m.name}.token_emb.weight"], self.touched[i]) for i, m in enumerate(self.mods)]
+        self.touched = [torch.zeros(m.vocab_size, device=self.dev, dtype=torch.uint8) for m in self.enc_mods]
+        return [(self.g[f"encoder_embeddings.{m.name}.token_emb.weight"], self.touched[i]) for i, m in enumerate(self.enc_mods)]
 
     def resize_workspaces(self, max_batch: int, n_enc: int, n_dec: int):
         """Re-allocate the activation workspaces for another (batch, N, M); parameters are untouched."""
@@ -1416,7 +1448,10 @@ class Engine:
         R = sum(B * n for _, _, n, _ in parts)
         x, xn = w["xa"], w["xb"]
         for side, enc_inputs, N, r0 in parts:          # N = rows per sample, the engine's register tokens included
-            mods = [m for m in self.mods if m.name in enc_inputs]
+            foreign = [k for k in enc_inputs if k not in {m.name for m in self.enc_mods}]
+            if foreign:
+                raise KeyError(f"an encoder pass takes encoder modalities only (generate.py:749-751): {foreign}")
+            mods = [m for m in self.enc_mods if m.name in enc_inputs]
             ops.compact([enc_inputs[m.name][1].contiguous() for m in mods], [enc_inputs[m.name][0].reshape(B, -1).contiguous() for m in mods],
                         None, [m.max_tokens for m in mods], [m.id for m in mods], N - self.R, False, side, B, n_reg=self.R)
             ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods], [self.pos[m.name] for m in mods],
@@ -1440,7 +1475,7 @@ class Engine:
         different contexts (parts[g] = (side, N_g, first context row); groups with an empty context last).  Everything
         but the cross-attention itself is one launch for all groups.  Returns bf16 logits [groups * B * M, V]."""
         cfg, D = self.cfg, self.D
-        tm = {m.name: m for m in self.mods}[target]
+        tm = {m.name: m for m in self.dec_mods}[target]          # (KeyError: the target must be a decoder modality)
         B, M = dec_pos.shape
         G = len(parts)
         RM, RD = B * M, G * B * M
@@ -1453,7 +1488,7 @@ class Engine:
         y, yn = w["ya"], w["yb"]
         local = dec_pos.to(self.dev, I32)
         local = (local.unsqueeze(0).expand(G, B, M) if G > 1 else local).contiguous()
-        ops.embed_fwd(None, [self.pos[tm.name]], [self.p[f"encoder_embeddings.{tm.name}.mod_emb"]], self.p["mask_token"],
+        ops.embed_fwd(None, [self.pos[tm.name]], [self.p[self.dec_mod_emb_key[tm.name]]], self.p["mask_token"],
                       w["dslot"], local, w["dtok"], y, None, RD, D)
         w["full_m"].fill_(M)
         all_keys = _keys_per_sample(w["zero_b"], w["full_m"])       # decoder self-attention is unmasked (sa_mask=None)
@@ -1579,7 +1614,7 @@ class Engine:
         `run(ws, static sets, static dec_pos, out)` over them (`_graphed`, keyed by key(modality names)), then copy-in and replay.
         Returns the static bf16 logits [len(sets) * B * M, V]: valid until the next replay of the same graph."""
         B, M = dec_pos.shape
-        names = tuple(m.name for m in self.mods if m.name in sets[0])
+        names = tuple(m.name for m in self.enc_mods if m.name in sets[0])
 
         def make_state():
             return {"ws": alloc(),
@@ -1605,7 +1640,7 @@ class Engine:
         ~300 kernel launches of a pass are replayed with one host call, the logits land in a static buffer
         that stays valid until the next replay of the same graph."""
         B, M = dec_pos.shape
-        V = {m.name: m for m in self.mods}[target].vocab_size
+        V = {m.name: m for m in self.dec_mods}[target].vocab_size
         out = self._replay(lambda names: (B, names, int(n_enc), M, target), [enc_inputs], dec_pos, V,
                            lambda: self._alloc_infer(B, max(int(n_enc) + self.R, 1), M, fresh=True),
                            lambda ws, sets, pos, out: self.infer_logits(sets[0], n_enc, target, pos, out=out, ws=ws))
@@ -1614,7 +1649,7 @@ class Engine:
     def infer_logits_cfg_graphed(self, enc_cond, n_cond: int, enc_uncond, n_uncond: int, target: str, dec_pos: torch.Tensor):
         """`infer_logits_cfg` (both passes of a guided step, one decoder pass) replayed from a captured hipGraph"""
         B, M = dec_pos.shape
-        V = {m.name: m for m in self.mods}[target].vocab_size
+        V = {m.name: m for m in self.dec_mods}[target].vocab_size
         out = self._replay(lambda names: ("cfg", B, names, int(n_cond), int(n_uncond), M, target), [enc_cond, enc_uncond], dec_pos, V,
                            lambda: self._alloc_infer(B, max(int(n_cond), int(n_uncond), 1) + self.R, M, fresh=True, groups=2),
                            lambda ws, sets, pos, out: self.infer_logits_cfg(sets[0], n_cond, sets[1], n_uncond, target, pos, out=out, ws=ws))

@@ -152,7 +152,7 @@ class GenerationSampler:
     def _enc_inputs(self, mod_dict, n_enc: Optional[int] = None):
         eng = self.engine
         enc = {}
-        for m in eng.mods:
+        for m in eng.enc_mods:                 # (encoder modalities only, generate.py:749-751: a decoder-only target never re-enters)
             if m.name not in mod_dict:
                 continue
             d = mod_dict[m.name]
@@ -362,8 +362,9 @@ class GenerationSampler:
             cond = list(info.get("cfg_cond_domains", []))
             guided = info.get("cfg_scale", 1.0) != 1.0 and len(cond) > 0
             # rows kept by a pass = max over the batch of the unmasked inputs of all its modalities (:413-415)
-            total = int(sum(n_in[n] + dec_so_far[n] for n in names).max())
-            unc = [n for n in names if n not in cond]
+            enc_names = [n for n in names if n in {m.name for m in eng.enc_mods}]
+            total = int(sum(n_in[n] + dec_so_far[n] for n in enc_names).max()) if enc_names else 0
+            unc = [n for n in enc_names if n not in cond]
             total_u = int(sum(n_in[n] + dec_so_far[n] for n in unc).max()) if unc else 0
             plan.append(dict(target=t, n_dec=n_dec, n_rows=n_rows, scheme=scheme, n_enc_cond=total, guided=guided, n_enc_uncond=total_u, info=info))
             dec_so_far[t] += n_dec

@@ -23,6 +23,27 @@ from . import ops
 from .synth import MOD4_MIXTURE_ALPHAS, _key
 
 _WHOLE = ("img", "cam", "gaze", "keypoints")
+ALPHA_EPS = 1e-9          # the reference's floor under every Dirichlet alpha (egom2p/data/masking.py:159-165: torch.clamp(alphas, min=eps))
+
+
+def sampling_mod_info(in_domains: Sequence[str], out_domains: Sequence[str], modality_info: Dict[str, Dict],
+                      input_alphas: Optional[Sequence[float]] = None, target_alphas: Optional[Sequence[float]] = None) -> Dict[str, Dict]:
+    """The masking `modality_info` of a dataset with its own input / output modalities (`setup_sampling_mod_info`,
+    egom2p/data/pretrain_utils.py:30-63): the entries of in_domains | out_domains, `input_alphas` 0 outside in_domains,
+    `target_alphas` 0 outside out_domains.  Order: in_domains as given, then the output-only ones (the reference sorts the names; the
+    budget stream is drawn per position, and a dataset with in_domains == out_domains keeps the order - and the draws - it always had) - a modality with alpha 0 (floored at ALPHA_EPS by UnifiedMasking) gets a
+    token budget of 0 on that side.  input_alphas / target_alphas: one mixture (a list of alphas, one per component) shared by the
+    side's domains; None: the symmetric mod4 mixture."""
+    ins, outs = list(in_domains), list(out_domains)
+    a_in = list(MOD4_MIXTURE_ALPHAS if input_alphas is None else input_alphas)
+    a_tg = list(MOD4_MIXTURE_ALPHAS if target_alphas is None else target_alphas)
+    assert len(a_in) == len(a_tg), "one alpha per mixture component on either side"
+    info = {}
+    for m in ins + [m for m in outs if m not in ins]:
+        info[m] = dict(modality_info[m])
+        info[m]["input_alphas"] = list(a_in) if m in ins else [0.0] * len(a_in)
+        info[m]["target_alphas"] = list(a_tg) if m in outs else [0.0] * len(a_tg)
+    return info
 
 
 def _pair(x) -> Tuple[int, int]:
@@ -48,7 +69,8 @@ class UnifiedMasking:
             per_mod = [list(modality_info[n].get(key, MOD4_MIXTURE_ALPHAS)) for n in self.names]
             n_mix = len(per_mod[0])
             assert all(len(a) == n_mix for a in per_mod), f"{key}: every modality needs one alpha per mixture component"
-            return [[per_mod[i][j] for i in range(len(self.names))] for j in range(n_mix)]          # [n_mix][n_mods]
+            # (alpha 0 = "never sample this modality on this side": floored like the reference's Dirichlet, :159-165)
+            return [[max(float(per_mod[i][j]), ALPHA_EPS) for i in range(len(self.names))] for j in range(n_mix)]          # [n_mix][n_mods]
         self.in_alphas, self.tgt_alphas = alphas("input_alphas"), alphas("target_alphas")
         assert len(self.in_alphas) == len(self.tgt_alphas)
         self.weights = [1.0] * len(self.in_alphas) if sampling_weights is None else [float(w) for w in sampling_weights]
@@ -105,4 +127,22 @@ def causal_decoder_intervals(mod_mask) -> Tuple[np.ndarray, np.ndarray]:
             if r > 0 and mm[b, r] != mm[b, r - 1]:
                 g0 = r
             ks[b, r], ke[b, r] = g0, r + 1
+    return ks, ke
+
+
+def nosep_decoder_intervals(mod_mask, dam, causal: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """Key intervals of the decoder's self-attention under `decoder_sep_mask=False`, on the host: the rule ego_compact_nosep applies
+    on the device (csrc/embed.hip), restated in numpy for tests and tools.
+
+    mod_mask: int [B, M] as for `causal_decoder_intervals`; dam: int [B, M], the gathered decoder_attention_mask of the kept rows.
+    Returns (ks, ke) int32 [B, M]: a valid row r sees the keys [0, cumsum(dam)_r) cut at M - adapt_decoder_attention_mask without its
+    separation term (egom2p_model.py:465-474) - or, causal, [0, r + 1) (:459-463); a padding row gets every valid key [0, n_valid)."""
+    mm = np.asarray(mod_mask).astype(np.int64)
+    cs = np.cumsum(np.asarray(dam).astype(np.int64), axis=1)
+    B, M = mm.shape
+    ks, ke = np.zeros((B, M), np.int32), np.zeros((B, M), np.int32)
+    for b in range(B):
+        nv = int((mm[b] >= 0).sum())
+        for r in range(M):
+            ke[b, r] = nv if mm[b, r] < 0 else (r + 1 if causal else min(int(cs[b, r]), M))
     return ks, ke

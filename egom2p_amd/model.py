@@ -10,7 +10,9 @@ buffer) and `forward` / `loss.backward()` run the hand-written HIP kernels.
 Scope: the SwiGLU / bias-free / LayerNorm(no-bias) variants and the GELU family (plain Mlp under an erf
 GELU, `qkv_bias` / `proj_bias` / `mlp_bias`, LayerNorm with bias - the `*_gelu` registrations, egom2p_model.py:881-978) with token
 modalities (`VideoToken*`, `GazeCamToken*` embeddings), with the standard or the causal decoder mask (`decoder_causal_mask`,
-always with `decoder_sep_mask=True`); `forward` takes a `mod_dict` holding any non-empty subset of the configured modalities.
+with or without the modality separation `decoder_sep_mask`); `forward` takes a `mod_dict` holding any non-empty subset of the configured modalities.
+The encoder and the decoder may hold different modality sets (an rgb -> depth specialist: encoder {rgb}, decoder {depth}); a decoder-only
+modality owns its `mod_emb`, and `share_modality_embeddings=False` gives every decoder modality one of its own.
 Stochastic depth (`drop_path_rate_encoder`, `drop_path_rate_decoder`, `shared_drop_path`; egom2p_model.py:96-98, 137-154) drops
 residual branches per sample in `model.train()` forwards under grad mode - decisions drawn on the device from
 `engine.set_drop_path_seed(seed, counter)` - and is inactive under `model.eval()`, `torch.no_grad()`, `return_logits` and generation.
@@ -150,10 +152,10 @@ class EgoM2P(nn.Module):
         if mlp is None: unsupported.append("non-SwiGLU MLP" if act_layer is not nn.GELU or gated_mlp else "MLP")
         if mlp == "swiglu" and mlp_bias: unsupported.append("mlp_bias with the gated MLP")
         if not hasattr(probe, "eps"): unsupported.append("norm_layer without eps")
-        # (decoder_causal_mask=True is supported together with the modality separation: one key interval per decoder row)
-        if not decoder_sep_mask: unsupported.append("decoder_sep_mask=False")
-        if not share_modality_embeddings: unsupported.append("unshared modality embeddings")
-        if set(encoder_embeddings) != set(decoder_embeddings): unsupported.append("different encoder/decoder modality sets")
+        # (decoder_causal_mask / decoder_sep_mask in any combination: one key interval per decoder row either way.  The encoder and
+        #  the decoder may hold different modality sets - run_training_egom2p.py:354-389 builds them from --in_domains / --out_domains -
+        #  and share_modality_embeddings=False gives every decoder modality a mod_emb of its own, egom2p_model.py:179-183)
+        if not encoder_embeddings or not decoder_embeddings: unsupported.append("a model without encoder or without decoder embeddings")
         if unsupported:
             raise NotImplementedError("outside the MI355X hot-path scope (SURVEY.md section 8): " + ", ".join(unsupported))
         self.modality_info = modality_info
@@ -166,7 +168,9 @@ class EgoM2P(nn.Module):
         self.encoder_modalities, self.decoder_modalities = set(encoder_embeddings), set(decoder_embeddings)
         share = all(getattr(e, "share_embedding", True) for e in decoder_embeddings.values())
         mods = []
-        for name, emb in encoder_embeddings.items():
+        # the model's modalities: the encoder's in their order, then the decoder-only ones in theirs
+        both = list(encoder_embeddings.items()) + [(n, e) for n, e in decoder_embeddings.items() if n not in encoder_embeddings]
+        for name, emb in both:
             info = modality_info[name]
             kind = "video" if isinstance(emb, VideoTokenEncoderEmbedding) else "seq1d"
             grid = (5, emb.image_size // emb.patch_size[1], emb.image_size // emb.patch_size[2]) if kind == "video" else (0, 0, 0)
@@ -182,7 +186,11 @@ class EgoM2P(nn.Module):
                             mlp=mlp, qkv_bias=bool(qkv_bias), proj_bias=bool(proj_bias), mlp_bias=bool(mlp_bias), norm_bias=norm_bias,
                             qk_norm=bool(qk_norm), drop_path_rate_encoder=float(drop_path_rate_encoder),
                             drop_path_rate_decoder=float(drop_path_rate_decoder), shared_drop_path=bool(shared_drop_path),
-                            use_act_checkpoint=bool(use_act_checkpoint))
+                            use_act_checkpoint=bool(use_act_checkpoint),
+                            encoder_modalities=tuple(m.name for m in mods if m.name in encoder_embeddings),
+                            decoder_modalities=tuple(m.name for m in mods if m.name in decoder_embeddings),
+                            share_modality_embeddings=bool(share_modality_embeddings), decoder_sep_mask=bool(decoder_sep_mask))
+        self.share_modality_embeddings = bool(share_modality_embeddings)
         # ModelCfg.mods looks names up in MODALITIES: custom vocab / positions go through a private table
         self._device = device or ("cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else None)
         if self._device is None:
@@ -351,14 +359,17 @@ class EgoM2P(nn.Module):
         # averages the loss over those; a key without an embedding raises, as its embedding lookup would
         if not mod_dict:
             raise ValueError("mod_dict is empty")
-        unknown = [k for k in mod_dict if k not in self.encoder_modalities]
+        unknown = [k for k in mod_dict if k not in self.encoder_modalities and k not in self.decoder_modalities]
         if unknown:
             raise KeyError(f"mod_dict holds modalities this model has no embeddings for: {unknown}")
         names = [m.name for m in self._mods if m.name in mod_dict]
         B = mod_dict[names[0]]["tensor"].shape[0]
-        # (argsort(...)[:, :n] of the reference cannot keep more rows than the present modalities have positions)
-        t_present = sum(m.max_tokens for m in self._mods if m.name in mod_dict)
-        self._ensure(B, min(num_encoder_tokens, t_present), min(num_decoder_tokens, t_present))
+        # (argsort(...)[:, :n] of the reference cannot keep more rows than the present modalities of that side have positions)
+        t_enc = sum(m.max_tokens for m in self._mods if m.name in mod_dict and m.name in self.encoder_modalities)
+        t_dec = sum(m.max_tokens for m in self._mods if m.name in mod_dict and m.name in self.decoder_modalities)
+        if not t_enc or not t_dec:
+            raise ValueError("mod_dict holds no " + ("encoder" if not t_enc else "decoder") + " modality of this model")
+        self._ensure(B, min(num_encoder_tokens, t_enc), min(num_decoder_tokens, t_dec))
         md = {}
         for n in names:
             d = mod_dict[n]
@@ -367,7 +378,9 @@ class EgoM2P(nn.Module):
                      "target_mask": d["target_mask"].to(self._device, torch.bool).contiguous(),
                      "decoder_attention_mask": d["decoder_attention_mask"].to(self._device, torch.int32).contiguous()}
         # the reference shuffles the decoder modality order with python's global `random` (egom2p_model.py:312)
-        order = [k for k, _ in random.sample(list(md.items()), len(md))]
+        # (cat_decoder_tensors walks the keys that have a decoder embedding, :308-312: an encoder-only entry takes no part in the draw)
+        dec_items = [kv for kv in md.items() if kv[0] in self.decoder_modalities]
+        order = [k for k, _ in random.sample(dec_items, len(dec_items))]
         if return_logits:
             return self.engine.forward_logits(md, order)
         # stochastic depth is active where the reference's DropPath is (egom2p_utils.py:93, 112: `self.training`) and a backward can follow

@@ -436,11 +436,12 @@ def adamw_step_gated(p, g, m, v, lr, wd, step, gate, beta1=0.9, beta2=0.95, eps=
 
 
 def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0,
-            causal=False):
+            causal=False, sep=True):
     """`out`: dict of preallocated tensors (ids_keep,pad,mod_mask,slot,local,tok,ks,ke,n_valid,seg,err), n_reg + n_keep entries per
     sample (n_reg: register tokens in front of the kept rows, encoder only).
     causal (decoder side only): the key intervals of `decoder_causal_mask=True` (ego_compact_causal; masking.causal_decoder_intervals
-    states the rule on the host)."""
+    states the rule on the host).  sep=False (decoder side only): `decoder_sep_mask=False`, the intervals without the modality
+    separation (ego_compact_nosep, with or without causal; masking.nosep_decoder_intervals states the rule on the host)."""
     d = L.CompactDesc()
     d.n_mods, d.n_keep, d.is_decoder, d.n_reg = len(masks), n_keep, int(is_decoder), int(n_reg)
     for i in range(len(masks)):
@@ -452,6 +453,9 @@ def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_
     for k in ("ids_keep", "pad", "mod_mask", "slot", "local", "tok", "ks", "ke", "n_valid", "seg", "err"):
         setattr(d, k, out[k].data_ptr())
     d.seg_bad = out["seg_bad"].data_ptr() if out.get("seg_bad") is not None else None
+    if not sep:
+        check(L.load().ego_compact_nosep(C.byref(d), B, int(bool(causal)), _stream()), "ego_compact_nosep")
+        return
     if causal:
         check(L.load().ego_compact_causal(C.byref(d), B, _stream()), "ego_compact_causal")
         return

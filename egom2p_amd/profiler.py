@@ -142,7 +142,7 @@ class KernelTimer:
         }
         # HBM-bound front-end / bookkeeping kernels: algorithmic bytes (the index streams once, only
         # the kept rows of the tables / positional tables, every output once)
-        def c_compact(masks, ids, dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0, causal=False):
+        def c_compact(masks, ids, dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0, causal=False, sep=True):
             T = sum(n_pos)
             return 0.0, float(B) * (T * (1 + (4 if is_decoder else 0)) + (n_keep + n_reg) * (8 + 31))
 

@@ -344,8 +344,11 @@ def masking_budgets_host(cfg: ModelCfg, batch: int, n_in_range=(2048, 2048), n_t
 
 def masking_budgets_device(cfg: ModelCfg, batch: int, n_in_range=(2048, 2048), n_tgt_range=(2048, 2048), seed: int = 0,
                            sample_offset: int = 0, alphas: Sequence[float] = MOD4_MIXTURE_ALPHAS,
-                           mix_weights: Optional[Sequence[float]] = None, min_tokens: int = 0, device: str = "cuda"):
-    """Token budgets of `batch` clips sampled ON THE DEVICE (ego_budget_dirichlet): int32 tensors [n_mods, batch]."""
+                           mix_weights: Optional[Sequence[float]] = None, min_tokens: int = 0, device: str = "cuda",
+                           in_names: Optional[Sequence[str]] = None, tgt_names: Optional[Sequence[str]] = None):
+    """Token budgets of `batch` clips sampled ON THE DEVICE (ego_budget_dirichlet): int32 tensors [n_mods, batch].
+    in_names / tgt_names: the modalities that may be inputs / targets (None: all) - the others get alpha 0 on that side
+    (egom2p/data/pretrain_utils.py:34-63), which the launch floors at 1e-9: a budget of 0."""
     from . import ops
     mods = cfg.mods
     keys = np.array([_key(f"clip{sample_offset + b}.budget", seed) for b in range(batch)], dtype=np.uint64)
@@ -353,7 +356,9 @@ def masking_budgets_device(cfg: ModelCfg, batch: int, n_in_range=(2048, 2048), n
     k_in = torch.empty(len(mods), batch, dtype=torch.int32, device=device)
     k_tg = torch.empty(len(mods), batch, dtype=torch.int32, device=device)
     al = [[a] * len(mods) for a in alphas]
-    ops.budget_dirichlet(kd, al, al, [1.0] * len(alphas) if mix_weights is None else mix_weights, [m.max_tokens for m in mods],
+    al_in = al if in_names is None else [[a if m.name in in_names else 0.0 for m in mods] for a in alphas]
+    al_tg = al if tgt_names is None else [[a if m.name in tgt_names else 0.0 for m in mods] for a in alphas]
+    ops.budget_dirichlet(kd, al_in, al_tg, [1.0] * len(alphas) if mix_weights is None else mix_weights, [m.max_tokens for m in mods],
                          [min_tokens] * len(mods), [True] * len(mods), n_in_range, n_tgt_range, k_in, k_tg)
     return k_in, k_tg
 
@@ -363,7 +368,9 @@ def make_clip_batch_device_masked(cfg: ModelCfg, batch: int, n_in: int = 2048, n
     """Synthetic clips whose budgets come from the reference's Dirichlet mixture, budgets AND masks made on the device:
     nothing but the per-clip stream keys crosses the host-device boundary."""
     from . import ops
-    k_in, k_tg = masking_budgets_device(cfg, batch, (n_in, n_in), (n_tgt, n_tgt), seed, sample_offset, device=device)
+    # (an asymmetric model: inputs among its encoder modalities only, targets among its decoder modalities only)
+    k_in, k_tg = masking_budgets_device(cfg, batch, (n_in, n_in), (n_tgt, n_tgt), seed, sample_offset, device=device,
+                                        in_names=cfg.encoder_modalities, tgt_names=cfg.decoder_modalities)
     out: Dict[str, Dict[str, torch.Tensor]] = {}
     for j, m in enumerate(cfg.mods):
         n = m.max_tokens

@@ -34,12 +34,12 @@ class TrainStep:
         skip = ()
         if (world_size > 1 or force_reducer) and sparse_tables != "off" and clips_per_step is not None:
             cap = clips_per_step * engine.N
-            V = max(m.vocab_size for m in engine.mods)
+            V = max(m.vocab_size for m in engine.enc_mods)
             if sparse_tables == "on" or SparseTableExchange.worth_it(V, engine.D, cap, world_size):
                 # small tables (cam / gaze: 256 rows) stay on the dense path: only tables the rule favours are exchanged
-                picked = [(g, fl, m) for (g, fl), m in zip(engine.track_touched_table_rows(True), engine.mods)
+                picked = [(g, fl, m) for (g, fl), m in zip(engine.track_touched_table_rows(True), engine.enc_mods)
                           if sparse_tables == "on" or SparseTableExchange.worth_it(m.vocab_size, engine.D, cap, world_size)]
-                for i, m in enumerate(engine.mods):
+                for i, m in enumerate(engine.enc_mods):
                     if all(m is not pm for _, _, pm in picked):
                         engine.touched[i] = None
                 if picked:
@@ -59,7 +59,7 @@ class TrainStep:
     def __call__(self, micro_batches: Sequence[Dict[str, Dict[str, torch.Tensor]]], lr: Optional[float] = None,
                  weight_decay: Optional[float] = None):
         eng = self.engine
-        names = [m.name for m in eng.mods]
+        names = [m.name for m in eng.dec_mods]
         k = len(micro_batches)
         if self.sparse is not None:
             # the row lists are sized for clips_per_step clips: more would drop touched rows from the exchange (replicas diverge)

@@ -29,7 +29,8 @@ extern "C" {
  * ego_maskgit_positions / ego_maskgit_select; 9: causal decoder variant - new ego_compact_causal; 10: the GELU / biased
  * family - EGO_EPI_BIAS_BF16, new ego_gelu_fwd / ego_gelu_bwd, ego_layernorm_bias_fwd / ego_layernorm_bias_bwd, ego_bias_grad
  * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; 12: stochastic depth -
- * new ego_droppath_draw / ego_droppath_resid / ego_droppath_scale; loaders must refuse other versions) */
+ * new ego_droppath_draw / ego_droppath_resid / ego_droppath_scale; loaders must refuse other versions.  Added under 12 without a
+ * bump (no existing entry or struct changed): ego_compact_nosep, the decoder compaction of decoder_sep_mask=False) */
 #define EGO_ABI_VERSION 12
 #define EGO_MAX_MODS 8
 
@@ -98,6 +99,14 @@ int ego_compact(const ego_compact_desc* d, int B, hipStream_t stream);
  * (its rows do not share one interval: ego_attn_*_d64_seg must take the per-row path).  The reference adds register tokens on
  * the encoder side only (:381-387): n_reg must be 0 here; the cross-attention keys (registers included) are not affected. */
 int ego_compact_causal(const ego_compact_desc* d, int B, hipStream_t stream);
+/* The decoder side under `decoder_sep_mask=False` (adapt_decoder_attention_mask, egom2p/models/egom2p_model.py:446-481 without the
+ * separation term of :476-479), with the cumsum rule (causal = 0, :465-474) or triu(1) (causal = 1, :459-463).  Same descriptor and
+ * outputs as ego_compact with is_decoder = 1 (required, n_reg = 0), except the key intervals, which start at key 0 and run across the
+ * slots' segments: causal = 0: [ks, ke) = [0, cs) for a kept row whose cumulative decoder_attention_mask sum is cs (cut at n_keep),
+ * `err` raised as by ego_compact when a padding key would be visible (cs > n_valid with padding present); causal = 1: [0, r + 1)
+ * for kept row r, `dam` not read, `err` never raised.  Padding rows get [0, n_valid).  seg_bad[b] is raised whenever a kept row's
+ * interval is not exactly its slot's segment (any sample with two non-empty slots): ego_attn_*_d64_seg then takes the per-row path. */
+int ego_compact_nosep(const ego_compact_desc* d, int B, int causal, hipStream_t stream);
 
 /* Fused embedding of the kept rows: x = token_row + (pos_row + mod_emb), emb = pos_row + mod_emb;
  * padding rows are zero.  Replaces the embedding modules' forward (encoder_embeddings.py:181-210,

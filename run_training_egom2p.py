@@ -158,8 +158,9 @@ class ShardClips:
 
     def __init__(self, args, model, epoch, rank, world, steps, seed, device):
         from egom2p_amd.data import TokenShards
-        from egom2p_amd.masking import UnifiedMasking
-        info = {m: MODALITY_INFO[m] for m in args.in_domains}
+        from egom2p_amd.masking import UnifiedMasking, sampling_mod_info
+        # in_domains | out_domains, alpha 0 for inputs outside in_domains and targets outside out_domains (pretrain_utils.py:30-63)
+        info = sampling_mod_info(args.in_domains, args.out_domains, MODALITY_INFO)
         # the shard shuffle must be the same on every rank (it is dealt rank::world afterwards): args.seed, not seed + rank
         self.ds = TokenShards(args.data_path, args.batch_size, rank=rank, world=world, shuffle_seed=args.seed,
                               vocab={m: int(i["vocab_size"]) for m, i in info.items()})
