@@ -133,6 +133,8 @@ _SIGS = {
     "ego_adamw_step": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, i32, vp],
     "ego_adamw_gate": [vp, f32, f32, i32, vp, vp],
     "ego_adamw_step_gated": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, i32, vp, vp],
+    "ego_ema_update": [vp, vp, i64, f32, f32, vp],
+    "ego_swap_f32": [vp, vp, i64, vp],
     "ego_sample_cfg_topp": [vp, vp, i64, i32, f32, f32, i32, f32, vp, vp, vp, i32, vp],
     "ego_maskgit_positions": [vp, i32, i32, i32, vp, vp],
     "ego_maskgit_select": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],

@@ -205,3 +205,77 @@ extern "C" int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long
     LAUNCH_CHECK();
     return EGO_OK;
 }
+
+// ---- model EMA: a moving average of the flat parameter buffer, and the in-place exchange that applies it ---------------------
+//
+// Replaces: ModelEmaV2.update (egom2p/utils/timm/model_ema.py:128-132: `ema_v.copy_(decay * ema_v + (1 - decay) * model_v)` per
+// state-dict tensor) by one pass over the flat buffer, and the deepcopy'd module of :111 by exchanging the contents of the two
+// buffers (parameter views and captured graphs keep their addresses).  Both are HBM-bound streams: 12 and 16 B per element.
+namespace {
+
+// one fma: the same expression in the vector body and in the tail, whatever the compiler would contract
+__device__ __forceinline__ float ema_one(float e, float p, float d, float omd) { return fmaf(d, e, omd * p); }
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float d,
+                                                         float omd) {
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 ee = *(f32x4*)(ema + i * 4);
+        const f32x4 pp = *(const f32x4*)(p + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ee[e] = ema_one(ee[e], pp[e], d, omd);
+        *(f32x4*)(ema + i * 4) = ee;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long i = n4 * 4; i < n; ++i) ema[i] = ema_one(ema[i], p[i], d, omd);
+}
+
+// bit patterns, not values: 32-bit integer loads and stores, no arithmetic (NaN payloads, -0.0 and denormals survive)
+__global__ __launch_bounds__(256) void swap_u32_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const u32x4 va = *(const u32x4*)(a + i * 4), vb = *(const u32x4*)(b + i * 4);
+        *(u32x4*)(a + i * 4) = vb;
+        *(u32x4*)(b + i * 4) = va;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long i = n4 * 4; i < n; ++i) {
+            const unsigned t = a[i];
+            a[i] = b[i];
+            b[i] = t;
+        }
+}
+
+// two ranges of n floats each: both given, 16-byte aligned, disjoint
+bool flat_pair_ok(const void* a, const void* b, long n) {
+    if (!a || !b || ((uintptr_t)a) % 16 || ((uintptr_t)b) % 16) return false;
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b;
+    const uintptr_t hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    return hi - lo >= (uintptr_t)n * sizeof(float);
+}
+
+int flat_blocks(long n) {       // the grid adamw_kernel takes: capped, the kernels stride over the rest with 64-bit indices
+    const long n4 = n / 4;
+    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+    return blocks < 1 ? 1 : blocks;
+}
+
+}  // namespace
+
+extern "C" int ego_ema_update(float* ema, const float* p, long n, float decay, float one_minus_decay, hipStream_t stream) {
+    if (n < 0 || !(decay >= 0.f && decay <= 1.f) || !(one_minus_decay >= 0.f && one_minus_decay <= 1.f)) return EGO_ERR_ARG;
+    if (n == 0) return EGO_OK;
+    if (!flat_pair_ok(ema, p, n)) return EGO_ERR_ARG;
+    EGO_LAUNCH(ema_update_kernel, dim3(flat_blocks(n)), dim3(256), 0, stream, ema, p, n, decay, one_minus_decay);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
+extern "C" int ego_swap_f32(float* a, float* b, long n, hipStream_t stream) {
+    if (n < 0) return EGO_ERR_ARG;
+    if (n == 0) return EGO_OK;
+    if (!flat_pair_ok(a, b, n)) return EGO_ERR_ARG;
+    EGO_LAUNCH(swap_u32_kernel, dim3(flat_blocks(n)), dim3(256), 0, stream, (unsigned*)a, (unsigned*)b, n);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}

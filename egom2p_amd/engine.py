@@ -232,6 +232,7 @@ class Engine:
         self.q8, self.qs, self._q_of = None, None, None      # fp8 GEMMs: e4m3 copy + row scales of the current GEMM input, and whose it is
         self._alloc_workspaces()
         self.weights_dirty = True
+        self.params_swapped = False                     # inside ModelEma.applied(): P holds the averaged weights (ema.py)
         self._have_fwd = False
         self.fmods, self.femods = self.dec_mods, self.enc_mods      # the decoder / encoder modalities of the last forward (a mod_dict may hold a subset)
         self._ce_done, self._ce_grad = set(), None      # modalities whose CE backward ran inside the forward (loss_grad)

@@ -31,7 +31,7 @@ TASKS = {
 }
 
 
-def main(task: str = "rgb2depth"):
+def get_parser(task: str = "rgb2depth") -> argparse.ArgumentParser:
     t = TASKS[task]
     ap = argparse.ArgumentParser(description=f"{task} generation (ROAR or MaskGIT, {t['steps']} steps, CFG 2.0, top-p 0.8)")
     ap.add_argument("--model", default="egom2p_base_12e_12d_swiglu_nobias")
@@ -47,17 +47,39 @@ def main(task: str = "rgb2depth"):
     ap.add_argument("--token-schedule", choices=["linear", "cosine"], default="linear",
                     help="tokens per step of --scheme maskgit (ROAR is always linear, generate.py:272-275)")
     ap.add_argument("--temp-schedule", default="constant", help="constant, linear or onex:{min_t}:{power} (generate.py:280-289)")
-    args = ap.parse_args()
+    ap.add_argument("--use-ema", action="store_true",
+                    help="generate with the averaged weights: load --ckpt's `state_dict_ema` (written by run_training_egom2p.py "
+                         "--model_ema; the reference's key, model_ema.py:137) instead of `model`")
+    return ap
+
+
+def load_weights(model, ckpt: str, use_ema: bool = False):
+    """weights_only=True: nothing from the file is executed"""
+    key = "state_dict_ema" if use_ema else "model"
+    ck = torch.load(ckpt, map_location="cpu", weights_only=True)
+    if key not in ck:
+        raise SystemExit(f"--use-ema: {ckpt} holds no `state_dict_ema` (train with run_training_egom2p.py --model_ema)" if use_ema
+                         else f"{ckpt} holds no `model` state dict")
+    model.load_state_dict(ck[key])
+
+
+def main(task: str = "rgb2depth", argv=None, **model_kwargs):
+    """argv: the command line (None: sys.argv); model_kwargs: constructor keywords for `create_model` - the registered variant
+    at another width or depth, as the tests build it.  Returns the generated `mod_dict`."""
+    t = TASKS[task]
+    args = get_parser(task).parse_args(argv)
+    if args.use_ema and not args.ckpt:
+        raise SystemExit("--use-ema needs --ckpt: a checkpoint that holds `state_dict_ema`")
     if args.scheme == "roar":
         args.token_schedule = "linear"
     torch.set_grad_enabled(False)
     device = "cuda"
     mods = ["tok_rgb", "tok_depth", "tok_cam", "tok_gaze"]
     model = create_model(args.model, encoder_embeddings={m: MODALITY_INFO[m]["encoder_embedding"]() for m in mods},
-                         decoder_embeddings={m: MODALITY_INFO[m]["decoder_embedding"]() for m in mods}, modality_info=MODALITY_INFO)
+                         decoder_embeddings={m: MODALITY_INFO[m]["decoder_embedding"]() for m in mods}, modality_info=MODALITY_INFO,
+                         **model_kwargs)
     if args.ckpt:
-        # weights_only=True: nothing from the file is executed
-        model.load_state_dict(torch.load(args.ckpt, map_location="cpu", weights_only=True)["model"])
+        load_weights(model, args.ckpt, use_ema=args.use_ema)
     model.eval()
     sampler = GenerationSampler(model, use_graphs=(not args.no_graphs) and args.graph == "pass")
     whole = (not args.no_graphs) and args.graph == "schedule"
@@ -102,3 +124,4 @@ def main(task: str = "rgb2depth"):
                           "graph": "none" if args.no_graphs else args.graph, "batch": args.batch, "s_per_clip": dt / args.batch,
                           "clips_per_s": args.batch / dt, "passes_per_clip": passes, "ms_per_pass": dt / passes * 1e3}))
     print(f"done: {t['target']} tokens", tuple(out[t["target"]]["tensor"].shape))
+    return out

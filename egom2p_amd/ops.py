@@ -435,6 +435,29 @@ def adamw_step_gated(p, g, m, v, lr, wd, step, gate, beta1=0.9, beta2=0.95, eps=
                                         _p(sqnorm), int(zero_grad), _p(gate), _stream()), "ego_adamw_step_gated")
 
 
+def _flat_f32(name, *ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.EgoHipError(f"{name}: contiguous float32 tensors")
+    if any(t.numel() != ts[0].numel() for t in ts):
+        raise L.EgoHipError(f"{name}: the two ranges differ in length")
+
+
+def ema_update(ema, p, decay):
+    """ema = decay * ema + (1 - decay) * p over flat fp32 buffers (model_ema.py:128-132).  `1 - decay` is formed here in double
+    and rounded once: the kernel takes both factors."""
+    _flat_f32("ema_update", ema, p)
+    d = float(decay)
+    check(L.load().ego_ema_update(_p(ema), _p(p), ema.numel(), d, 1.0 - d, _stream()), "ego_ema_update")
+
+
+def swap_f32(a, b):
+    """Exchange the contents of two flat fp32 buffers in place, bit for bit."""
+    _flat_f32("swap_f32", a, b)
+    check(L.load().ego_swap_f32(_p(a), _p(b), a.numel(), _stream()), "ego_swap_f32")
+
+
 def compact(masks: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], dams, n_pos, mod_ids, n_keep, is_decoder, out, B, n_reg=0,
             causal=False, sep=True):
     """`out`: dict of preallocated tensors (ids_keep,pad,mod_mask,slot,local,tok,ks,ke,n_valid,seg,err), n_reg + n_keep entries per

@@ -118,6 +118,9 @@ class FusedAdamW:
         inf or NaN (the reference steps on a NaN norm: `nan >= thr` is false).  Both are decided on the device; a gated call
         leaves parameters, moments and every tensor's step count as they were and still clears the gradients."""
         eng = self.engine
+        if getattr(eng, "params_swapped", False):
+            raise RuntimeError("FusedAdamW.step inside ModelEma.applied(): the flat buffer holds the averaged weights, "
+                               "a step here would train the average")
         gated = skip_grad is not None or bool(skip_nonfinite)
         if skip_grad is not None and not skip_grad > 0:
             raise ValueError(f"skip_grad must be positive, got {skip_grad}")

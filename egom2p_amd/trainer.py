@@ -20,13 +20,17 @@ class TrainStep:
     def __init__(self, engine: Engine, lr: float = 1e-4, weight_decay: float = 0.05, clip_grad: Optional[float] = 1.0,
                  process_group=None, world_size: int = 1, seed: int = 0, force_reducer: bool = False,
                  clips_per_step: Optional[int] = None, sparse_tables: str = "auto", dp_algo: Optional[str] = None,
-                 dp_backend: str = "torch"):
+                 dp_backend: str = "torch", ema=None):
         """clips_per_step (per rank) bounds the table rows one step can touch (clips x kept encoder tokens); with
         sparse_tables = "auto" the encoder tables' gradients go through the row-list exchange when that moves fewer bytes
         than the dense all-reduce ("on" / "off" force it).  dp_algo: "allreduce" | "rs_ag" (GradBucketReducer); dp_backend:
         "torch" (torch.distributed's RCCL) or "cabi" (the library's own communicator, ego_dp_*; GPU groups only).
-        Activation checkpointing is the engine's own setting (`Engine(act_checkpoint=True)`): the step drives either engine alike."""
+        Activation checkpointing is the engine's own setting (`Engine(act_checkpoint=True)`): the step drives either engine alike.
+        ema: an `ema.ModelEma` of this engine, updated after every optimiser step (None: no average is kept)."""
         self.engine = engine
+        if ema is not None and ema.engine is not engine:
+            raise ValueError("TrainStep: the ModelEma belongs to another engine")
+        self.ema = ema
         self.opt = FusedAdamW(engine, lr=lr, weight_decay=weight_decay, world_size=world_size)
         self.clip = clip_grad
         self.sparse = None
@@ -83,4 +87,6 @@ class TrainStep:
         if weight_decay is not None:
             self.opt.param_groups[0]["weight_decay"] = weight_decay
         norm = self.opt.step(clip_grad=self.clip, zero_grad=True)
+        if self.ema is not None:
+            self.ema.update()
         return self.loss_sum / k, norm

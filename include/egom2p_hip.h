@@ -30,7 +30,8 @@ extern "C" {
  * family - EGO_EPI_BIAS_BF16, new ego_gelu_fwd / ego_gelu_bwd, ego_layernorm_bias_fwd / ego_layernorm_bias_bwd, ego_bias_grad
  * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; 12: stochastic depth -
  * new ego_droppath_draw / ego_droppath_resid / ego_droppath_scale; loaders must refuse other versions.  Added under 12 without a
- * bump (no existing entry or struct changed): ego_compact_nosep, the decoder compaction of decoder_sep_mask=False) */
+ * bump (no existing entry or struct changed): ego_compact_nosep, the decoder compaction of decoder_sep_mask=False; ego_ema_update /
+ * ego_swap_f32, the model EMA - tests/test_droppath_kernels_gpu.py pins version 12, and new entries alone do not call for a bump) */
 #define EGO_ABI_VERSION 12
 #define EGO_MAX_MODS 8
 
@@ -505,6 +506,20 @@ int ego_adamw_gate(const double* sqnorm, float gscale, float skip_norm, int skip
 int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long n, float lr, float wd, float beta1, float beta2, float eps,
                          int step, float gscale, float max_norm, const double* sqnorm, int zero_grad, const int* gate,
                          hipStream_t stream);
+
+/* Model EMA over the flat parameter buffer (ModelEmaV2.update, egom2p/utils/timm/model_ema.py:128-132:
+ * `ema_v.copy_(decay * ema_v + (1. - decay) * model_v)` for every state-dict tensor): ema[i] = decay * ema[i] + one_minus_decay * p[i]
+ * in fp32 (one fma), p read-only, one pass of 12 B per element.  BOTH factors are arguments: the caller forms 1 - decay in double
+ * and rounds once (1.0f - 0.9999f is off by 1.7e-4 of the small factor; the rounding of decay itself can cost up to 3e-4 there).  Any n >= 0 (n == 0: nothing is launched): 16-byte
+ * vector body, scalar tail; capped grid with 64-bit strides.  No atomics, no allocation, no sync: capturable.
+ * EGO_ERR_ARG: a NULL or not 16-byte aligned pointer, ema == p or overlapping ranges, a factor outside [0, 1] or NaN, n < 0. */
+int ego_ema_update(float* ema, const float* p, long n, float decay, float one_minus_decay, hipStream_t stream);
+/* Exchanges a[0, n) and b[0, n) in place, without a third buffer - what stands in for the reference's deep-copied EMA module
+ * (egom2p/utils/timm/model_ema.py:128-132 keeps the average in `self.module`, :111; here evaluating with the average means
+ * exchanging the flat buffer's contents, so parameter views and captured graphs keep their addresses).  Bit patterns move, not
+ * values (32-bit integer loads and stores, no arithmetic): NaN payloads, infinities, -0.0 and denormals survive; two calls are
+ * the identity.  n and the refusals as above. */
+int ego_swap_f32(float* a, float* b, long n, hipStream_t stream);
 
 /* ---- data-parallel gradient exchange (RCCL over xGMI) ---------------------------------------- */
 

@@ -35,6 +35,7 @@ sys.path.insert(0, ROOT)
 from egom2p_amd import synth  # noqa: E402
 from egom2p_amd.config import MODALITIES, MODEL_CFGS, ModelCfg  # noqa: E402
 from egom2p_amd.dp import DataParallel, init_distributed_mode  # noqa: E402
+from egom2p_amd.ema import ModelEma  # noqa: E402
 from egom2p_amd.model import MODALITY_INFO, create_model  # noqa: E402
 from egom2p_amd.optim import NativeScalerWithGradNormCount, create_optimizer  # noqa: E402
 from egom2p_amd.scheduler import build_schedules  # noqa: E402
@@ -73,6 +74,12 @@ def get_args(argv=None):
     p.add_argument("--skip_grad", default=None, type=float, help="Skip update if gradient norm larger than threshold (default: %(default)s)")
     p.add_argument("--skip_nonfinite_grad", action="store_true",
                    help="pass an update by when its gradient norm is inf or NaN (decided on the device; not in the reference)")
+    p.add_argument("--model_ema", action="store_true",
+                   help="keep a moving average of the weights on the device (ModelEmaV2, egom2p/utils/timm/model_ema.py:84-149): updated after "
+                        "every optimiser step, evaluated beside the model, saved as state_dict_ema (+4 B per parameter)")
+    p.add_argument("--model_ema_decay", default=0.9999, type=float, help="ema = decay * ema + (1 - decay) * model")
+    p.add_argument("--model_ema_warmup", action="store_true",
+                   help="decay of update k is min(decay, (1 + k) / (10 + k)): a short run does not keep its initial weights")
     p.add_argument("--weight_decay", default=0.05, type=float)
     p.add_argument("--weight_decay_end", default=None, type=float, help="final weight decay (default: constant)")
     p.add_argument("--blr", default=1e-4, type=float, help="base lr: lr = blr * global_batch / 256")
@@ -179,9 +186,11 @@ class ShardClips:
             yield self.mask({k: v.to(self.device, non_blocking=True) for k, v in batch.items() if k in self.mask.names})
 
 
-def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, lr_values, device, wd_values=None):
+def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, lr_values, device, wd_values=None, model_ema=None):
     """reference :678-797, minus the per-step host syncs.  `start_steps` = epoch * steps per epoch: the schedules are indexed
-    by the loader step like the reference's (:702); during the frozen-model epochs only the embeddings train (:686-693)."""
+    by the loader step like the reference's (:702); during the frozen-model epochs only the embeddings train (:686-693).
+    model_ema (--model_ema): updated after every optimiser call - one the step gate passed by included, as the reference's
+    call pattern has it (the decision stays on the device; the average then moves toward unchanged weights)."""
     model.train()
     if args.frozen_model_epochs > 0 and epoch < args.frozen_model_epochs:
         if args.frozen_embedding_domain is None:
@@ -209,6 +218,8 @@ def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, 
                                        num_decoder_tokens=args.num_target_tokens, loss_type=args.loss_type)
                 grad_norm = scaler(loss / args.accum_iter, optimizer, clip_grad=args.clip_grad, skip_grad=args.skip_grad,
                                    parameters=model.parameters(), update_grad=True)
+                if model_ema is not None:
+                    model_ema.update()
             else:
                 with model.no_sync():
                     loss, mod_loss = model(mod_dict, num_encoder_tokens=args.num_input_tokens,
@@ -265,6 +276,35 @@ def evaluate(model, loader, device, args, prefix="[Eval] "):
     return out
 
 
+def checkpoint_dict(model, optimizer, epoch, args, model_ema=None):
+    """What a checkpoint-N.pth holds (tensors, numbers, strings: loadable with weights_only=True).  With --model_ema: the
+    reference's top-level `state_dict_ema` (model_ema.py:137: the averaged weights under the model's own keys) and `ema`, the
+    average's decay, warm-up flag and update count."""
+    ck = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "epoch": epoch,
+          "args": {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, list, type(None)))}}
+    if model_ema is not None:
+        sd = model_ema.state_dict()
+        ck["state_dict_ema"] = sd.pop("state_dict_ema")
+        ck["ema"] = sd
+    return ck
+
+
+def load_checkpoint(ck, model, optimizer=None, model_ema=None):
+    """Restore what `checkpoint_dict` saved; returns the epoch to continue at.  An average without a saved state starts from
+    the loaded weights, with the reference's notice (model_ema.py:149)."""
+    model.load_state_dict(ck["model"])
+    if optimizer is not None and "optimizer" in ck:
+        optimizer.load_state_dict(ck["optimizer"])
+    if model_ema is not None:
+        if "state_dict_ema" in ck:
+            model_ema.load_state_dict({"state_dict_ema": ck["state_dict_ema"], **ck.get("ema", {})})
+            print("Loaded state_dict_ema", flush=True)
+        else:
+            model_ema.set()
+            print("Failed to find state_dict_ema, starting from loaded model weights", flush=True)
+    return int(ck.get("epoch", -1)) + 1
+
+
 def main(args):
     distributed = init_distributed_mode(args)
     rank = args.rank if distributed else 0
@@ -277,6 +317,8 @@ def main(args):
     args.lr = args.blr * global_batch / 256                      # reference :498-505
     model = DataParallel(model)
     optimizer = create_optimizer(args, model.module)
+    # (every rank keeps its own average: the ranks' parameters are bitwise equal after every step, so the averages are too)
+    model_ema = ModelEma(model.module, decay=args.model_ema_decay, warmup=args.model_ema_warmup) if args.model_ema else None
     scaler = NativeScalerWithGradNormCount(enabled=False, skip_nonfinite=args.skip_nonfinite_grad)   # bf16: GradScaler disabled (:518)
     # ---- epochs / warm-up / cool-down / frozen phase from token budgets (reference :433-470); an "epoch" is epoch_size clips
     tok_per_clip = args.num_input_tokens + args.num_target_tokens
@@ -318,10 +360,7 @@ def main(args):
             args.resume = os.path.join(args.output_dir, f"checkpoint-{max(have)}.pth")
     if args.resume:
         ck = torch.load(args.resume, map_location="cpu", weights_only=True)
-        model.module.load_state_dict(ck["model"])
-        if "optimizer" in ck:
-            optimizer.load_state_dict(ck["optimizer"])
-        first_epoch = int(ck.get("epoch", -1)) + 1
+        first_epoch = load_checkpoint(ck, model.module, optimizer, model_ema)
         if rank == 0:
             print(f"resumed {args.resume}: continuing at epoch {first_epoch}, loader step {first_epoch * steps_per_epoch}", flush=True)
     for epoch in range(first_epoch, epochs):
@@ -336,7 +375,7 @@ def main(args):
         else:
             loader = SyntheticClips(mcfg, args.batch_size, args.num_input_tokens, args.num_target_tokens, steps_per_epoch,
                                     seed=seed * 1000 + epoch, mask=args.mask, device=device)
-        stats = train_one_epoch(model, loader, optimizer, scaler, args, epoch, epoch * steps_per_epoch, lr_values, device, wd_values)
+        stats = train_one_epoch(model, loader, optimizer, scaler, args, epoch, epoch * steps_per_epoch, lr_values, device, wd_values, model_ema)
         if args.eval_steps > 0 and ((epoch + 1) % max(1, args.eval_freq) == 0 or epoch + 1 == epochs):
             # held-out clips (reference :641-649): shards of --eval_data_path, or synthetic clips from a seed stream no training
             # epoch uses; the decoder-order stream is re-seeded so that every evaluation sees the same batches and orders
@@ -348,6 +387,11 @@ def main(args):
                 ev_loader = SyntheticClips(mcfg, args.batch_size, args.num_input_tokens, args.num_target_tokens, args.eval_steps,
                                            seed=(seed + 7919) * 1000 + 999, mask=args.mask, device=device)
             stats.update(evaluate(model, ev_loader, device, args))
+            if model_ema is not None:
+                # the same held-out batches and decoder orders through the averaged weights (the loaders are re-iterable)
+                random.seed(seed * 1000 + 999_983)
+                with model_ema.applied():
+                    stats.update(evaluate(model, ev_loader, device, args, prefix="[Eval EMA] "))
         if rank == 0:
             print(json.dumps({"epoch": epoch, **stats}), flush=True)
             if args.output_dir:
@@ -356,8 +400,7 @@ def main(args):
                     f.write(json.dumps({"epoch": epoch, **stats}) + "\n")
             if args.output_dir:
                 os.makedirs(args.output_dir, exist_ok=True)
-                torch.save({"model": model.module.state_dict(), "optimizer": optimizer.state_dict(), "epoch": epoch,
-                            "args": {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, list, type(None)))}},
+                torch.save(checkpoint_dict(model.module, optimizer, epoch, args, model_ema),
                            os.path.join(args.output_dir, f"checkpoint-{epoch}.pth"))
         if args.max_steps > 0:
             break
