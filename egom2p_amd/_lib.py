@@ -54,6 +54,14 @@ class EmbedBwdDesc(C.Structure):
     ]
 
 
+class PosembGradDesc(C.Structure):
+    _fields_ = [
+        ("dx", vp), ("d2", vp), ("slot", vp), ("local", vp), ("rows", i64), ("rows_per_sample", i32), ("B", i32), ("D", i32),
+        ("ld", i64), ("n_mods", i32), ("n_pos", i32 * MAX_MODS), ("dpos", vp * MAX_MODS), ("accumulate", i32),
+        ("work", vp), ("work_ints", i64), ("err", vp),
+    ]
+
+
 class HeadNormOp(C.Structure):
     _fields_ = [("x", vp), ("x_bs", i64), ("x_rs", i64), ("y", vp), ("y_bs", i64), ("y_rs", i64),
                 ("w", vp), ("mean", vp), ("rstd", vp), ("dw", vp)]
@@ -72,6 +80,8 @@ _SIGS = {
     "ego_embed_bwd_work_floats": [i64, i32, i32],
     "ego_embed_bwd": [C.POINTER(EmbedBwdDesc), vp],
     "ego_reg_grad": [vp, i32, i64, i32, i32, vp, vp],
+    "ego_posemb_grad_work_ints": [i32, i32, C.POINTER(i32)],
+    "ego_posemb_grad": [C.POINTER(PosembGradDesc), vp],
     "ego_rows_compact": [vp, i32, i32, vp, vp, vp],
     "ego_rows_gather": [vp, vp, vp, i32, i32, vp, vp],
     "ego_rows_scatter": [vp, vp, vp, i32, i32, vp, i32, vp],
@@ -171,7 +181,7 @@ def load():
         for name, args in _SIGS.items():
             fn = getattr(lib, name)
             fn.argtypes = args
-            fn.restype = i64 if name.endswith(("_work_floats", "_split_floats")) else i32
+            fn.restype = i64 if name.endswith(("_work_floats", "_split_floats", "_work_ints")) else i32
         if lib.ego_abi_version() != ABI_VERSION:
             raise EgoHipError(f"libegom2p_hip.so ABI version {lib.ego_abi_version()} != binding {ABI_VERSION}: rebuild (make -C egom2p_amd/csrc)")
         # kernel experiments: EGO_GEMM_NT256 / EGO_GEMM_TN256 = 0 | 1 | 2 pick the GEMM tile family (the library itself

@@ -81,6 +81,11 @@ class ModelCfg:
     share_modality_embeddings: bool = True
     # the modality separation of the decoder's self-attention mask (adapt_decoder_attention_mask, egom2p_model.py:476-479)
     decoder_sep_mask: bool = True
+    # learned positional tables (`sincos_pos_emb=False`, encoder_embeddings.py:138, 226, 255-260 and the same lines of
+    # decoder_embeddings.py): the modalities whose encoder / decoder embedding holds pos_emb as an nn.Parameter (1, n_pos, dim),
+    # N(0, 0.02), instead of the fixed sin-cos buffer - one flag per embedding module, so per side and modality; () = none
+    learned_pos_emb_encoder: Tuple[str, ...] = ()
+    learned_pos_emb_decoder: Tuple[str, ...] = ()
 
     @property
     def head_dim(self) -> int:

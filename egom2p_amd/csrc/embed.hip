@@ -772,6 +772,187 @@ extern "C" int ego_reg_grad(const float* dx, int B, long rows_per_sample, int n_
     return EGO_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// gradient of learned positional tables: dpos[m][p] (+)= sum_b (dx + d2)[row of sample b at (m, p)], b ascending.
+//
+// A scatter over the rows turned into a gather per destination through an inverse index (no atomics, bitwise reproducible):
+//   * posgrad_index_kernel: inv[(moff[m] + p) * B + b] = row, over a buffer the launcher set to -1.  A sample holds a position
+//     at most once, so every store is unique; rows outside the contract (slot >= n_mods, local outside the table) raise err.
+//   * posgrad_sum_kernel: one wave per (m, p).  Lane b holds inv[.][b] (one coalesced load per 64 samples), the valid entries are
+//     walked in ascending b, K rows in flight (a kept position is held by ~ a fifth of the samples: a dependent load per sample
+//     would leave the wave latency-bound).  In front of that every workgroup checks its share of the rows: a row that does not
+//     find itself in the index lost its entry to another row of the same sample and (m, p) - err.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct PosGradArgs {
+    const float* dx; const float* d2;
+    const int* slot; const int* local;
+    float* dpos[EGO_MAX_MODS];
+    int n_pos[EGO_MAX_MODS];
+    int moff[EGO_MAX_MODS + 1];        // first destination of modality m (a fixed table owns none); moff[n_mods] = all destinations
+    long rows, ld;
+    int rps, B, D, n_mods, accumulate;
+    int* inv; int* err;
+};
+
+// destination index of row r's (slot, local) or -1 (not a row of a learned table); bad = outside the contract
+__device__ __forceinline__ int posgrad_dest(const PosGradArgs& a, long r, bool& bad) {
+    bad = false;
+    const int s = a.slot[r];
+    if (s < 0) return -1;
+    if (s >= a.n_mods) { bad = true; return -1; }
+    bool has = false;
+    int np = 0, off = 0;
+#pragma unroll
+    for (int m = 0; m < EGO_MAX_MODS; ++m) if (m == s) { has = a.dpos[m] != nullptr; np = a.n_pos[m]; off = a.moff[m]; }
+    if (!has) return -1;
+    const int p = a.local[r];
+    if (p < 0 || p >= np) { bad = true; return -1; }
+    return off + p;
+}
+
+__global__ __launch_bounds__(256) void posgrad_index_kernel(PosGradArgs a) {
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < a.rows; r += (long)gridDim.x * 256) {
+        bool bad;
+        const int t = posgrad_dest(a, r, bad);
+        // The word belongs to this call while it runs (other writers - ego_compact, ego_loss_finalize - are ordered by the stream),
+        // so every thread that gets here reads the caller's value or that value | 2 and stores that value | 2: no atomic needed.
+        if (bad) *a.err = *a.err | 2;
+        if (t >= 0) a.inv[(long)t * a.B + (int)(r / a.rps)] = (int)r;
+    }
+}
+
+template <int MAXC>
+__global__ __launch_bounds__(256) void posgrad_sum_kernel(PosGradArgs a) {
+    constexpr int K = MAXC <= 4 ? 4 : 2;               // rows in flight per wave (K * 2 * MAXC 16-byte loads)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // ---- this workgroup's share of the rows: does the index hold the row?
+    {
+        const long per = (a.rows + gridDim.x - 1) / gridDim.x;
+        const long r0 = (long)blockIdx.x * per, r1 = min(a.rows, r0 + per);
+        for (long r = r0 + threadIdx.x; r < r1; r += 256) {
+            bool bad;
+            const int t = posgrad_dest(a, r, bad);
+            if (t >= 0 && a.inv[(long)t * a.B + (int)(r / a.rps)] != (int)r) *a.err = *a.err | 2;
+        }
+    }
+    // ---- one wave per destination
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= a.moff[a.n_mods]) return;
+    int m = 0;
+#pragma unroll
+    for (int k = 1; k < EGO_MAX_MODS; ++k) if (k < a.n_mods && t >= a.moff[k]) m = k;
+    float* tb = nullptr;
+    int off = 0;
+#pragma unroll
+    for (int k = 0; k < EGO_MAX_MODS; ++k) if (k == m) { tb = a.dpos[k]; off = a.moff[k]; }
+    if (!tb) return;
+    float* dst = tb + (long)(t - off) * a.ld;
+    // D need not be a multiple of 4 (dim 2046 in rows of 2048): nc 16-byte column groups, then lanes 0 .. (D & 3) - 1 take one
+    // column each of the tail [D & ~3, D) - the row pitch is a multiple of 4, so the groups stay aligned
+    const int nc = a.D >> 2, tcol = (nc << 2) + lane;
+    const bool tail = lane < (a.D & 3);
+    f32x4 acc[MAXC];
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float tacc = 0.f;
+    bool any = false;
+    for (int b0 = 0; b0 < a.B; b0 += 64) {
+        const int b = b0 + lane;
+        int e = b < a.B ? a.inv[(long)t * a.B + b] : -1;
+        if ((long)e >= a.rows) e = -1;                  // (the index holds rows only: a guard, not a case)
+        unsigned long long mask = __ballot(e >= 0);
+        any |= mask != 0ull;
+        while (mask) {
+            int ek[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                ek[k] = -1;
+                if (mask) { ek[k] = __shfl(e, __builtin_ctzll(mask), 64); mask &= mask - 1ull; }
+            }
+            f32x4 v[K][MAXC];
+            float tv[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                if (ek[k] < 0) continue;
+                const float* s1 = a.dx + (long)ek[k] * a.ld;
+                const float* s2 = a.d2 ? a.d2 + (long)ek[k] * a.ld : nullptr;
+                if (tail) { tv[k] = s1[tcol]; if (s2) tv[k] += s2[tcol]; }
+#pragma unroll
+                for (int i = 0; i < MAXC; ++i) {
+                    const int c = lane + 64 * i;
+                    if (c < nc) {
+                        v[k][i] = *(const f32x4*)(s1 + c * 4);
+                        if (s2) v[k][i] += *(const f32x4*)(s2 + c * 4);
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                if (ek[k] < 0) continue;
+#pragma unroll
+                for (int i = 0; i < MAXC; ++i) { const int c = lane + 64 * i; if (c < nc) acc[i] += v[k][i]; }
+                if (tail) tacc += tv[k];
+            }
+        }
+    }
+    if (a.accumulate && !any) return;                   // + 0: the row stays as it is
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nc) {
+            f32x4 o = acc[i];
+            if (a.accumulate) o += *(const f32x4*)(dst + c * 4);
+            *(f32x4*)(dst + c * 4) = o;
+        }
+    }
+    if (tail) dst[tcol] = a.accumulate ? tacc + dst[tcol] : tacc;
+}
+}  // namespace
+
+extern "C" long ego_posemb_grad_work_ints(int B, int n_mods, const int* n_pos) {
+    if (B <= 0 || n_mods <= 0 || n_mods > EGO_MAX_MODS || !n_pos) return 0;
+    long T = 0;
+    for (int m = 0; m < n_mods; ++m) T += n_pos[m] > 0 ? n_pos[m] : 0;
+    return T * B;
+}
+
+extern "C" int ego_posemb_grad(const ego_posemb_grad_desc* d, hipStream_t stream) {
+    if (!d || !d->dx || !d->slot || !d->local || !d->work || !d->err) return EGO_ERR_ARG;
+    if (d->rows <= 0 || d->rows > 0x7fffffffL || d->rows_per_sample <= 0 || d->B <= 0) return EGO_ERR_ARG;
+    if (d->D <= 0 || d->D > 2048 || d->ld < d->D || d->ld % 4) return EGO_ERR_ARG;          // (any D <= ld: a scalar tail behind D & ~3)
+    if (d->n_mods <= 0 || d->n_mods > EGO_MAX_MODS || d->rows > (long)d->B * d->rows_per_sample) return EGO_ERR_ARG;
+    uintptr_t al = (uintptr_t)d->dx | (uintptr_t)d->d2;
+    PosGradArgs a{};
+    bool learned = false;
+    long T = 0, Tall = 0;                               // destinations: of the learned tables (index, grid) / of all (the stated scratch)
+    for (int m = 0; m < d->n_mods; ++m) {
+        if (d->n_pos[m] <= 0) return EGO_ERR_ARG;
+        a.dpos[m] = d->dpos[m]; a.n_pos[m] = d->n_pos[m]; a.moff[m] = (int)T;
+        al |= (uintptr_t)d->dpos[m];
+        learned |= d->dpos[m] != nullptr;
+        Tall += d->n_pos[m];
+        if (d->dpos[m]) T += d->n_pos[m];               // a fixed table takes no index space, no memset bytes and no waves
+    }
+    if (al % 16 || Tall * d->B > 0x7fffffffL || d->work_ints < Tall * d->B) return EGO_ERR_ARG;
+    if (!learned) return EGO_OK;                        // every table fixed: nothing to do
+    for (int m = d->n_mods; m <= EGO_MAX_MODS; ++m) a.moff[m] = (int)T;
+    a.dx = d->dx; a.d2 = d->d2; a.slot = d->slot; a.local = d->local;
+    a.rows = d->rows; a.ld = d->ld; a.rps = d->rows_per_sample; a.B = d->B; a.D = d->D; a.n_mods = d->n_mods;
+    a.accumulate = d->accumulate ? 1 : 0; a.inv = d->work; a.err = d->err;
+    if (hipMemsetAsync(a.inv, 0xff, (size_t)T * d->B * sizeof(int), stream) != hipSuccess) return EGO_ERR_LAUNCH;
+    const long wg = (d->rows + 255) / 256;
+    EGO_LAUNCH(posgrad_index_kernel, dim3((unsigned)(wg < 2048 ? wg : 2048)), dim3(256), 0, stream, a);
+    LAUNCH_CHECK();
+    const dim3 grid((unsigned)((T + 3) / 4));
+    if (d->D <= 768) EGO_LAUNCH(posgrad_sum_kernel<3>, grid, dim3(256), 0, stream, a);
+    else if (d->D <= 1024) EGO_LAUNCH(posgrad_sum_kernel<4>, grid, dim3(256), 0, stream, a);
+    else if (d->D <= 1536) EGO_LAUNCH(posgrad_sum_kernel<6>, grid, dim3(256), 0, stream, a);
+    else EGO_LAUNCH(posgrad_sum_kernel<8>, grid, dim3(256), 0, stream, a);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
 extern "C" int ego_loss_perm(const int* seg, const int* canon, const int* slot, const int* tok, int B, int M,
                              int n_mods, int* perm, int* tgt_perm, int* ranges, int* base, hipStream_t stream) {
     if (B <= 0 || M <= 0 || n_mods <= 0 || n_mods > EGO_MAX_MODS) return EGO_ERR_ARG;

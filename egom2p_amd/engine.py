@@ -222,6 +222,12 @@ class Engine:
         enc_names = {m.name for m in self.enc_mods}
         self.dec_own_mod_emb = {m.name for m in self.dec_mods if not cfg.share_modality_embeddings or m.name not in enc_names}
         self.sep_mask = bool(cfg.decoder_sep_mask)
+        # learned positional tables (sincos_pos_emb=False): per side, the modalities whose pos_emb is a parameter in P / G
+        for side, names, have in (("encoder", cfg.learned_pos_emb_encoder, self.enc_mods), ("decoder", cfg.learned_pos_emb_decoder, self.dec_mods)):
+            unknown = [n for n in names if n not in {m.name for m in have}]
+            if unknown:
+                raise ValueError(f"learned_pos_emb_{side}: {unknown} not among the {side} modalities")
+        self.learned_enc, self.learned_dec = set(cfg.learned_pos_emb_encoder), set(cfg.learned_pos_emb_decoder)
         self.N, self.M, self.Bmax = n_enc, n_dec, max_batch
         # register tokens (egom2p_model.py:170-171, 381-387): R learned rows in front of every sample's N kept encoder tokens - the
         # encoder, the context and the cross-attention keys have Ne = R + N rows per sample; the compaction keeps N
@@ -349,6 +355,16 @@ class Engine:
             for m in self.dec_mods:
                 marks.append((f"to_logits.{m.name}", len(spec)))
                 add(f"decoder_embeddings.{m.name}.to_logits.weight", (m.vocab_size, D))
+        # learned positional tables behind everything else (a model without one keeps its layout): reference shape (1, n_pos, dim),
+        # decayed like mod_emb (no_weight_decay() is empty); one bucket, final with the encoder embedding backward
+        if self.learned_enc or self.learned_dec:
+            marks.append(("pos_emb", len(spec)))
+            for m in self.enc_mods:
+                if m.name in self.learned_enc:
+                    add(f"encoder_embeddings.{m.name}.pos_emb", (m.max_tokens, D))
+            for m in self.dec_mods:
+                if m.name in self.learned_dec:
+                    add(f"decoder_embeddings.{m.name}.pos_emb", (m.max_tokens, D))
 
         offs, total = {}, 0
         for name, shape in spec:
@@ -356,6 +372,8 @@ class Engine:
             offs[name] = (total, n, shape)
             total += (n + 3) // 4 * 4
         self.n_flat = total
+        # where the learned positional tables start: what lies in front is the flat layout of the same model with fixed tables
+        self.n_flat_body = min([o for k, (o, _, _) in offs.items() if k.endswith("pos_emb")], default=total)
         self.P = torch.zeros(total, device=self.dev, dtype=F32)
         self.G = torch.zeros(total, device=self.dev, dtype=F32)
         self.p: Dict[str, torch.Tensor] = {}
@@ -388,6 +406,9 @@ class Engine:
             pe = torch.zeros(m.max_tokens, D, device=self.dev, dtype=F32)
             pe[:, :self.Dl] = build_pos_emb(m, self.Dl)[0].to(self.dev)
             self.pos[m.name] = pe
+        # the table a side's embedding reads: the fixed one, or the side's own parameter
+        self.pos_enc = {m.name: self.p.get(f"encoder_embeddings.{m.name}.pos_emb", self.pos[m.name]) for m in self.enc_mods}
+        self.pos_dec = {m.name: self.p.get(f"decoder_embeddings.{m.name}.pos_emb", self.pos[m.name]) for m in self.dec_mods}
 
         # linear layers: bf16 copies
         self.lin: Dict[str, _Lin] = {}
@@ -426,8 +447,9 @@ class Engine:
 
     # reference key layout <-> engine storage ----------------------------------------------------
     def _is_buffer_key(self, key: str) -> bool:
-        """reference keys without storage here: pos tables are rebuilt, LN bias is a zero buffer (a parameter with norm_bias)"""
-        return key.endswith("pos_emb") or (not self.norm_bias and key.endswith(".bias") and "norm" in key)
+        """reference keys without storage here: fixed pos tables are rebuilt (a learned one is a parameter), LN bias is a zero buffer
+        (a parameter with norm_bias)"""
+        return (key.endswith("pos_emb") and key not in self.p) or (not self.norm_bias and key.endswith(".bias") and "norm" in key)
 
     def _view_for_key(self, key: str) -> Optional[torch.Tensor]:
         if self._is_buffer_key(key):
@@ -503,13 +525,13 @@ class Engine:
             if m.name in enc_names:
                 out[f"{e}.mod_emb"] = ref(f"{e}.mod_emb").view(1, 1, D)
                 out[f"{e}.token_emb.weight"] = ref(f"{e}.token_emb.weight")
-                out[f"{e}.pos_emb"] = self.pos[m.name][None, :, :D]
+                out[f"{e}.pos_emb"] = ref(f"{e}.pos_emb")[None] if m.name in self.learned_enc else self.pos[m.name][None, :, :D]
             if m.name in dec_names:
                 own = m.name in self.dec_own_mod_emb
                 out[f"{d}.mod_emb"] = ref(f"{d}.mod_emb").view(1, 1, D) if own else out[f"{e}.mod_emb"]
                 out[f"{d}.token_emb.weight"] = ref(f"{d}.token_emb.weight")
                 out[f"{d}.to_logits.weight"] = ref(self.logit_key[m.name])
-                out[f"{d}.pos_emb"] = self.pos[m.name][None, :, :D]
+                out[f"{d}.pos_emb"] = ref(f"{d}.pos_emb")[None] if m.name in self.learned_dec else self.pos[m.name][None, :, :D]
         zeros = torch.zeros(D, device=self.dev)
         for name in self.p:
             if name.startswith(("encoder.", "decoder.", "encoder_norm", "decoder_norm", "decoder_proj_context")):
@@ -541,7 +563,8 @@ class Engine:
             v = self._logical(ck, store[ck])
             if v.dim() <= 2:
                 shape = ((1, 1, self.Dl) if (ck.endswith("mod_emb") or ck == "mask_token") else
-                         (1, self.R, self.Dl) if ck == "register_tokens" else self._ref_shape(ck))
+                         (1, self.R, self.Dl) if ck == "register_tokens" else
+                         (1,) + self._ref_shape(ck) if ck.endswith("pos_emb") else self._ref_shape(ck))
                 v = v.view(shape)
             out.append(v)
         return out[0], out[1]
@@ -568,6 +591,8 @@ class Engine:
                 v.copy_((torch.rand(v.shape, device=self.dev, generator=gen) * 2 - 1) * a)
             elif name.endswith("token_emb.weight") or name.endswith("mod_emb") or name in ("mask_token", "register_tokens"):
                 v.copy_(torch.randn(v.shape, device=self.dev, generator=gen) * 0.02)
+            elif name.endswith("pos_emb"):
+                pass                                      # (drawn below, behind every other draw: the stream of the others does not move)
             elif name.endswith(".bias"):
                 v.zero_()                                 # (the biased family's own biases: drawn below, from their own generator)
             elif name.endswith("norm.weight") or ".norm" in name:
@@ -587,6 +612,13 @@ class Engine:
             if name.endswith(".bias") and name != "decoder_proj_context.bias":
                 v = self._view_for_key(name)
                 v.copy_(torch.randn(v.shape, device=self.dev, generator=bgen) * 0.05)
+        # learned positional tables: N(0, 0.02) (encoder_embeddings.py:168-169), from a generator of their own
+        pgen = torch.Generator(device=self.dev)
+        pgen.manual_seed(seed + 0x905E)
+        for name in self.p:
+            if name.endswith("pos_emb"):
+                v = self._view_for_key(name)
+                v.copy_(torch.randn(v.shape, device=self.dev, generator=pgen) * 0.02)
         self.weights_dirty = True
 
     def param_names(self) -> List[str]:
@@ -1143,10 +1175,10 @@ class Engine:
                     sep=self.sep_mask)
         x0 = self.enc[0]["x"] if cfg.encoder_depth else self.x_enc_out
         ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in emods],
-                      [self.pos[m.name] for m in emods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in emods],
+                      [self.pos_enc[m.name] for m in emods], [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in emods],
                       None, ce["slot"], ce["local"], ce["tok"], x0, self.emb_e, RN, D, reg=self.p["register_tokens"] if self.R else None)
         y0 = self.dec[0]["x"] if cfg.decoder_depth else self.y_out
-        ops.embed_fwd(None, [self.pos[m.name] for m in dmods], [self.p[self.dec_mod_emb_key[m.name]] for m in dmods],
+        ops.embed_fwd(None, [self.pos_dec[m.name] for m in dmods], [self.p[self.dec_mod_emb_key[m.name]] for m in dmods],
                       self.p["mask_token"], cd["slot"], cd["local"], cd["tok"], y0, None, RM, D)
         ckey = tuple(m.name for m in dmods)
         if ckey not in self._canon_dev:              # one small H2D copy per decoder order, ever (never inside a graph capture)
@@ -1329,6 +1361,7 @@ class Engine:
         dmods = self.dmods
         ops.embed_bwd(None, [self.g[self.dec_mod_emb_key[m.name]] for m in dmods], self.g["mask_token"],
                       dres, None, cd["slot"], cd["tok"], RM, D)
+        self._pos_grad("decoder", dmods, dres, None, cd, RM, M, B)
         done("head")
 
         # ---- context projection + encoder_norm
@@ -1354,13 +1387,29 @@ class Engine:
                       [self.g[f"encoder_embeddings.{m.name}.mod_emb"] for m in emods], None, dxe, self.dctx,
                       ce["slot"], ce["tok"], RN, D,
                       touched=None if self.touched is None else [self.touched[self.enc_mods.index(m)] for m in emods])
+        self._pos_grad("encoder", emods, dxe, self.dctx, ce, RN, N, B)
         if self.R:        # d register_tokens = the encoder input gradient of the register rows, summed over the batch (emb is 0 there)
             ops.reg_grad(dxe, B, N, self.R, D, self.g["register_tokens"])
         done("mod_emb")
         for m in reversed(self.enc_mods):
             done(f"enc_table.{m.name}")
+        if self.learned_enc or self.learned_dec:
+            done("pos_emb")           # (behind every other parameter in the flat buffer, final last: a bucket of its own)
         self._have_fwd = False
         self._ce_done = set()
+
+    def _pos_grad(self, side, mods, dx, d2, c, rows, rows_per_sample, B):
+        """Gradient of the learned positional tables of one side (mods: the side's modalities in slot order): the rows' dx (and, on the
+        encoder side, the gradient d2 of the `emb` added back onto the projected context, egom2p_model.py:722) summed per position
+        over the batch, accumulated into G.  A side without a learned table among `mods` launches nothing.
+        Rows that break the kernel's contract (one position twice in a sample, a position outside its table - ego_compact writes neither)
+        raise the DECODER compaction's error word, for either side: nothing clears it until the next forward's `loss_finalize`, which
+        then returns NaN losses and clears it - the stop the reference's non-finite-loss exit gives a wrong attention mask."""
+        learned = self.learned_enc if side == "encoder" else self.learned_dec
+        if not any(m.name in learned for m in mods):
+            return
+        ops.posemb_grad([self.g[f"{side}_embeddings.{m.name}.pos_emb"] if m.name in learned else m.max_tokens for m in mods],
+                        dx, d2, c["slot"], c["local"], rows, rows_per_sample, B, self.Dl, self.cd["err"], accumulate=True, ld=self.D)
 
     def zero_grad(self):
         self.G.zero_()
@@ -1455,7 +1504,7 @@ class Engine:
             mods = [m for m in self.enc_mods if m.name in enc_inputs]
             ops.compact([enc_inputs[m.name][1].contiguous() for m in mods], [enc_inputs[m.name][0].reshape(B, -1).contiguous() for m in mods],
                         None, [m.max_tokens for m in mods], [m.id for m in mods], N - self.R, False, side, B, n_reg=self.R)
-            ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods], [self.pos[m.name] for m in mods],
+            ops.embed_fwd([self.p[f"encoder_embeddings.{m.name}.token_emb.weight"] for m in mods], [self.pos_enc[m.name] for m in mods],
                           [self.p[f"encoder_embeddings.{m.name}.mod_emb"] for m in mods], None, side["slot"], side["local"], side["tok"],
                           x[r0:], w["emb"][r0:], B * N, D, reg=self.p["register_tokens"] if self.R else None)
 
@@ -1489,7 +1538,7 @@ class Engine:
         y, yn = w["ya"], w["yb"]
         local = dec_pos.to(self.dev, I32)
         local = (local.unsqueeze(0).expand(G, B, M) if G > 1 else local).contiguous()
-        ops.embed_fwd(None, [self.pos[tm.name]], [self.p[self.dec_mod_emb_key[tm.name]]], self.p["mask_token"],
+        ops.embed_fwd(None, [self.pos_dec[tm.name]], [self.p[self.dec_mod_emb_key[tm.name]]], self.p["mask_token"],
                       w["dslot"], local, w["dtok"], y, None, RD, D)
         w["full_m"].fill_(M)
         all_keys = _keys_per_sample(w["zero_b"], w["full_m"])       # decoder self-attention is unmasked (sa_mask=None)

@@ -16,6 +16,7 @@ modality owns its `mod_emb`, and `share_modality_embeddings=False` gives every d
 Stochastic depth (`drop_path_rate_encoder`, `drop_path_rate_decoder`, `shared_drop_path`; egom2p_model.py:96-98, 137-154) drops
 residual branches per sample in `model.train()` forwards under grad mode - decisions drawn on the device from
 `engine.set_drop_path_seed(seed, counter)` - and is inactive under `model.eval()`, `torch.no_grad()`, `return_logits` and generation.
+`sincos_pos_emb=False` on an embedding module makes that side's positional table of the modality a trained nn.Parameter (1, n_pos, dim).
 `use_act_checkpoint=True` (egom2p_model.py:82) builds a checkpointing engine: every block keeps its input only and is run again in
 front of its backward - the same losses, gradients and updates bit for bit, a fraction of the activation memory, one more pass over the blocks.
 Other variants raise NotImplementedError.
@@ -47,8 +48,9 @@ class _TokenEmbedding(nn.Module):
 
     def __init__(self, vocab_size: int, dim_tokens: Optional[int] = None, sincos_pos_emb: bool = True, **kwargs):
         super().__init__()
-        if not sincos_pos_emb:
-            raise NotImplementedError("learned positional embeddings are outside the hot-path scope")
+        # False: pos_emb is an nn.Parameter (1, n_pos, dim), N(0, init_std), of THIS embedding (encoder_embeddings.py:164-169) - the
+        # model turns the modules' flags into ModelCfg.learned_pos_emb_encoder / _decoder
+        self.sincos_pos_emb = bool(sincos_pos_emb)
         self.vocab_size, self.dim_tokens = vocab_size, dim_tokens
 
     def init(self, dim_tokens: int = 768, init_std: float = 0.02):
@@ -189,7 +191,9 @@ class EgoM2P(nn.Module):
                             use_act_checkpoint=bool(use_act_checkpoint),
                             encoder_modalities=tuple(m.name for m in mods if m.name in encoder_embeddings),
                             decoder_modalities=tuple(m.name for m in mods if m.name in decoder_embeddings),
-                            share_modality_embeddings=bool(share_modality_embeddings), decoder_sep_mask=bool(decoder_sep_mask))
+                            share_modality_embeddings=bool(share_modality_embeddings), decoder_sep_mask=bool(decoder_sep_mask),
+                            learned_pos_emb_encoder=tuple(m.name for m in mods if not getattr(encoder_embeddings.get(m.name), "sincos_pos_emb", True)),
+                            learned_pos_emb_decoder=tuple(m.name for m in mods if not getattr(decoder_embeddings.get(m.name), "sincos_pos_emb", True)))
         self.share_modality_embeddings = bool(share_modality_embeddings)
         # ModelCfg.mods looks names up in MODALITIES: custom vocab / positions go through a private table
         self._device = device or ("cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else None)
@@ -248,7 +252,7 @@ class EgoM2P(nn.Module):
 
         shared = {}
         for key, val in sd.items():
-            if key.endswith("pos_emb") or (not eng.norm_bias and key.endswith(".bias") and "norm" in key):
+            if eng._is_buffer_key(key):      # a fixed pos_emb (a learned one is a parameter); without norm_bias the LayerNorm bias
                 attach(self, key, val if (key.endswith("pos_emb") or val.shape != zeros.shape) else zeros, buffer=True)      # (with norm_bias the LayerNorm bias is a parameter)
                 continue
             val, g = eng.param_views(key)                  # views of the flat buffers (see Engine.param_views for their shapes)
@@ -289,7 +293,7 @@ class EgoM2P(nn.Module):
                 if dec_table and (tied or name.endswith("to_logits.weight")):
                     a = math.sqrt(6.0 / float(p.shape[0] + p.shape[1]))
                     p.uniform_(-a, a)
-                elif name.endswith("token_emb.weight") or name.endswith("mod_emb") or name in ("mask_token", "register_tokens"):
+                elif name.endswith(("token_emb.weight", "mod_emb", "pos_emb")) or name in ("mask_token", "register_tokens"):
                     p.normal_(0, self.init_std)                     # (register_tokens: nn.init.normal_(std=init_std), :172)
                 elif "norm" in name and name.endswith(".weight") and p.dim() == 1:
                     p.fill_(1.0)

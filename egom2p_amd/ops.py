@@ -520,6 +520,42 @@ def reg_grad(dx, B, rows_per_sample, n_reg, D, dreg):
     check(L.load().ego_reg_grad(_p(dx), B, rows_per_sample, n_reg, D, _p(dreg), _stream()), "ego_reg_grad")
 
 
+def posemb_grad_work_ints(B, n_mods, n_pos):
+    """int32 entries of scratch `posemb_grad` needs for B samples of modalities with n_pos[m] positions (the inverse index)"""
+    return int(L.load().ego_posemb_grad_work_ints(int(B), int(n_mods), (L.i32 * L.MAX_MODS)(*[int(n) for n in n_pos][:L.MAX_MODS])))
+
+
+_IWORK = {}
+
+
+def posemb_grad(dpos, dx, d2, slot, local, rows, rows_per_sample, B, D, err, accumulate=True, ld=None, work=None):
+    """Gradient of learned positional tables: dpos[m][p, :D] (+)= sum over the samples, in batch order, of (dx + d2)[row of the
+    sample with slot m, local p].  dpos: per modality slot one fp32 [n_pos, ld] tensor, or the int n_pos of a fixed table (skipped); dx / d2
+    (d2 may be None): what `embed_bwd` receives, rows of pitch ld (default: dx's).  err: int32 [1], |= 2 on a broken contract.
+    work: int32 scratch of posemb_grad_work_ints entries (default: one buffer per device, grown on demand)."""
+    _need_cuda(dx)
+    if len(dpos) > L.MAX_MODS:
+        raise L.EgoHipError(f"posemb_grad: at most {L.MAX_MODS} modalities")
+    d = L.PosembGradDesc()
+    n_pos = []
+    for i, t in enumerate(dpos):
+        fixed = isinstance(t, int)                    # a fixed table is given by its number of positions
+        d.dpos[i] = None if fixed else t.data_ptr()
+        d.n_pos[i] = t if fixed else t.shape[0]
+        n_pos.append(int(d.n_pos[i]))
+    d.dx, d.d2, d.slot, d.local = dx.data_ptr(), _p(d2), slot.data_ptr(), local.data_ptr()
+    d.rows, d.rows_per_sample, d.B, d.D = rows, rows_per_sample, B, D
+    d.ld = dx.stride(0) if ld is None else ld
+    d.n_mods, d.accumulate, d.err = len(dpos), int(bool(accumulate)), err.data_ptr()
+    if work is None:
+        n = posemb_grad_work_ints(B, len(dpos), n_pos)
+        work = _IWORK.get(dx.device)
+        if work is None or work.numel() < n:
+            work = _IWORK[dx.device] = torch.empty(int(n * 1.25) + 1024, device=dx.device, dtype=torch.int32)
+    d.work, d.work_ints = work.data_ptr(), work.numel()
+    check(L.load().ego_posemb_grad(C.byref(d), _stream()), "ego_posemb_grad")
+
+
 def rows_compact(touched, cap, rows, count):
     check(L.load().ego_rows_compact(_p(touched), touched.numel(), cap, _p(rows), _p(count), _stream()), "ego_rows_compact")
 

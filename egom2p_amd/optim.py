@@ -77,8 +77,8 @@ class FusedAdamW:
 
     def _active_runs(self):
         """Honour requires_grad=False (freeze_* methods of the model): frozen tensors are left untouched."""
-        if not self._named:
-            return self._runs
+        if not self._named and not any(self.skipped.values()):
+            return self._runs                       # (no tensor to freeze and none that sat steps out: the engine's own runs)
         sig = tuple(p.requires_grad for _, p in self._named)
         if sig != self._frozen_sig:
             self._fold_gated()                      # with the OLD frozen names, before the runs take their step offsets
@@ -184,6 +184,17 @@ class FusedAdamW:
             #  the element counts agree, the element ORDER does not - copying would misalign every moment behind `bridge` silently)
             raise RuntimeError("optimizer state without a storage-layout tag (saved before round 5): the flat parameter order changed since; "
                                "restart the optimizer state (the model state dict, keyed by name, still loads)")
+        body = int(getattr(self.engine, "n_flat_body", want[1]))
+        if (tuple(have) != tuple(want) and tuple(have[:1]) + tuple(have[2:]) == tuple(want[:1]) + tuple(want[2:])
+                and int(have[1]) == body < int(want[1]) and sd["m"].numel() == body):
+            # a run with fixed positional tables continued with learned ones: the learned tables lie behind everything the saved
+            # state covers, so the saved moments are the head of this engine's; the tables start like any parameter new to AdamW -
+            # zero moments, bias correction from step 1 (`skipped`, as for a tensor unfrozen later)
+            self.m.zero_(); self.v.zero_()
+            self.m[:body].copy_(sd["m"]); self.v[:body].copy_(sd["v"])
+            sd = dict(sd, m=self.m, v=self.v, layout=want,
+                      skipped=dict(sd.get("skipped", {}), **{n: int(sd["t"]) for n in self.engine.offsets if n.endswith("pos_emb")}))
+            have = want
         if tuple(have) != tuple(want):
             raise RuntimeError(f"optimizer state was saved for storage layout {tuple(have)}, this engine uses {tuple(want)} "
                                "(layout version, n_flat, D, heads stored, head pitch, padded F): resume with the same EGOM2P_HEAD_PAD / model, "

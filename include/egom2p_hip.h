@@ -31,7 +31,8 @@ extern "C" {
  * takes any width; 11: the QK-norm family - new ego_headnorm_fwd / ego_headnorm_bwd; 12: stochastic depth -
  * new ego_droppath_draw / ego_droppath_resid / ego_droppath_scale; loaders must refuse other versions.  Added under 12 without a
  * bump (no existing entry or struct changed): ego_compact_nosep, the decoder compaction of decoder_sep_mask=False; ego_ema_update /
- * ego_swap_f32, the model EMA - tests/test_droppath_kernels_gpu.py pins version 12, and new entries alone do not call for a bump) */
+ * ego_swap_f32, the model EMA; ego_posemb_grad / ego_posemb_grad_work_ints, the gradient of learned positional tables -
+ * tests/test_droppath_kernels_gpu.py pins version 12, and new entries alone do not call for a bump) */
 #define EGO_ABI_VERSION 12
 #define EGO_MAX_MODS 8
 
@@ -146,6 +147,37 @@ int ego_embed_bwd(const ego_embed_bwd_desc* d, hipStream_t stream);
  * egom2p_model.py:382): dreg[r] += sum over b (in batch order: bitwise reproducible) of dx[b * rows_per_sample + r], r < n_reg.
  * (ego_embed_bwd skips rows with a negative slot, the register rows among them.) */
 int ego_reg_grad(const float* dx, int B, long rows_per_sample, int n_reg, int D, float* dreg, hipStream_t stream);
+
+/* Gradient of LEARNED positional tables - `sincos_pos_emb=False` (encoder_embeddings.py:138, 226, 255-260 and the same lines of
+ * decoder_embeddings.py: pos_emb is an nn.Parameter (1, n_pos, dim) instead of a fixed sin-cos buffer), the backward of the
+ * `pos_emb` gather inside ego_embed_fwd:  dpos[m][p, :D] (+)= sum over samples b, ascending, of dx[r] + d2[r], r = the row of
+ * sample b with slot == m and local == p (dx / d2: what ego_embed_bwd receives - the gradient of x and of emb; d2 may be NULL).
+ * A position no sample holds gets + 0 (accumulate == 0: it is written as zero).  Columns [D, ld) of dpos are not touched.
+ * dpos[m] == NULL: modality m's table is fixed, its rows are skipped.  Rows with a negative slot (padding, registers) are skipped.
+ * Two launches behind a memset of `work`, no atomics of any kind - results are bitwise reproducible: (a) the inverse index
+ * inv[m][p][b] = row or -1 into `work` (every store unique); (b) one wave per (m, p) reads its B entries in one coalesced load,
+ * walks them in ascending b and sums the rows with 16-byte loads, several rows in flight; in front of that every workgroup checks
+ * for its share of the rows that the row finds itself in the index.  A sample that holds one (m, p) twice, a slot >= n_mods or a
+ * local outside [0, n_pos[m]) break the contract: err is raised (|= 2) and the row is left out (of two rows on one (m, p), one),
+ * nothing outside the tables is read or written.
+ * work: int32 scratch of at least ego_posemb_grad_work_ints(B, n_mods, n_pos) entries.  EGO_ERR_ARG: a NULL or not 16-byte aligned
+ * dx / dpos[m] / d2, NULL slot / local / work / err, ld < D, ld % 4 != 0, D > 2048, n_mods outside [1, EGO_MAX_MODS], n_pos[m] <= 0,
+ * rows > B * rows_per_sample, work_ints too small.  D itself may be any width <= ld (dim 2046 in rows of 2048: the columns behind
+ * D & ~3 are summed one per lane).  A fixed table costs nothing: it owns no index entries and no waves.  err is read-modify-written
+ * without atomics: while the call runs no other stream may write the word (ego_compact / ego_loss_finalize on the same stream are
+ * ordered); the engine hands in the decoder compaction's word, so a broken contract turns the next loss into NaN. */
+typedef struct {
+    const float* dx; const float* d2;        /* fp32 [rows, ld]; d2 may be NULL                                      */
+    const int* slot; const int* local;       /* int32 [rows], as ego_compact writes them                             */
+    long rows; int rows_per_sample, B, D; long ld;
+    int n_mods; int n_pos[EGO_MAX_MODS];
+    float* dpos[EGO_MAX_MODS];               /* fp32 [n_pos[m], ld] or NULL (fixed table)                            */
+    int accumulate;                          /* 0: dpos = sum, 1: dpos += sum                                        */
+    int* work; long work_ints;               /* int32 scratch (the inverse index)                                    */
+    int* err;                                /* in/out int32 [1]: |= 2 on a broken contract                          */
+} ego_posemb_grad_desc;
+long ego_posemb_grad_work_ints(int B, int n_mods, const int* n_pos);
+int ego_posemb_grad(const ego_posemb_grad_desc* d, hipStream_t stream);
 
 /* Row lists for the sparse data-parallel exchange of an embedding table's gradient (replaces, for few clips per step,
  * the dense all-reduce DDP performs on the 64000 x 768 tables, run_training_egom2p.py:514; encoder_embeddings.py:200,291).

@@ -66,6 +66,10 @@ def get_args(argv=None):
     p.add_argument("--act_checkpoint", action="store_true",
                    help="activation checkpointing per block (constructor keyword use_act_checkpoint): a layer keeps its input only and the "
                         "backward runs the block again - the same results bit for bit, less activation memory, more time per step")
+    p.add_argument("--learned_pos_emb", default="none", choices=["none", "encoder", "decoder", "both"],
+                   help="train the positional tables of that side's embeddings (their constructor keyword sincos_pos_emb=False: an "
+                        "nn.Parameter (1, n_pos, dim) per modality, N(0, 0.02)) instead of the fixed sin-cos buffers; a checkpoint of a "
+                        "sin-cos run loads into such a model, its fixed tables as the starting values")
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "bf16"])
     p.add_argument("--opt", default="adamw")
     p.add_argument("--opt_eps", default=1e-8, type=float)
@@ -123,8 +127,9 @@ def get_args(argv=None):
 
 def get_model(args):
     """reference :354-389"""
-    enc = {m: MODALITY_INFO[m]["encoder_embedding"]() for m in args.in_domains}
-    dec = {m: MODALITY_INFO[m]["decoder_embedding"]() for m in args.out_domains}
+    learned = getattr(args, "learned_pos_emb", "none")
+    enc = {m: MODALITY_INFO[m]["encoder_embedding"](sincos_pos_emb=learned not in ("encoder", "both")) for m in args.in_domains}
+    dec = {m: MODALITY_INFO[m]["decoder_embedding"](sincos_pos_emb=learned not in ("decoder", "both")) for m in args.out_domains}
     return create_model(args.model, encoder_embeddings=enc, decoder_embeddings=dec,
                         modality_info={m: MODALITY_INFO[m] for m in set(args.in_domains) | set(args.out_domains)},
                         num_register_tokens=args.num_register_tokens, **(dict(qk_norm=True) if args.qk_norm else {}),
