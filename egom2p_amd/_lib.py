@@ -67,6 +67,18 @@ class HeadNormOp(C.Structure):
                 ("w", vp), ("mean", vp), ("rstd", vp), ("dw", vp)]
 
 
+ADAMW_MAX_GROUPS, ADAMW_CHUNK, SEG_FROZEN = 128, 4096, 1     # EGO_ADAMW_MAX_GROUPS, EGO_ADAMW_CHUNK, EGO_SEG_FROZEN
+
+
+class AdamwSeg(C.Structure):
+    _fields_ = [("lo", i64), ("hi", i64), ("group", i32), ("flags", i32)]
+
+
+class AdamwHp(C.Structure):
+    _fields_ = [("lr", f32 * ADAMW_MAX_GROUPS), ("wd", f32 * ADAMW_MAX_GROUPS), ("bc1", f32 * ADAMW_MAX_GROUPS),
+                ("bc2_sqrt", f32 * ADAMW_MAX_GROUPS), ("step", i32 * ADAMW_MAX_GROUPS), ("n_groups", i32)]
+
+
 _SIGS = {
     "ego_abi_version": [],
     "ego_gemm_kernel_mode": [i32, i32],
@@ -156,6 +168,13 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
+
+# the extension entries of include/egom2p_hip_optim.h (same library; tests/test_param_groups_cpu.py holds header and table together)
+_SIGS_OPTIM = {
+    "ego_adamw_step_seg": [vp, vp, vp, vp, i64, C.POINTER(AdamwSeg), vp, i32, vp, C.POINTER(AdamwHp), f32, f32, f32, f32, f32, vp, i32,
+                           vp, vp],
+}
+EXPORTS_OPTIM = tuple(_SIGS_OPTIM)
 _lib = None
 
 
@@ -178,7 +197,7 @@ def load():
         if os.path.exists(hip_rt):
             C.CDLL(hip_rt, mode=C.RTLD_GLOBAL)
         lib = C.CDLL(LIB_PATH)
-        for name, args in _SIGS.items():
+        for name, args in {**_SIGS, **_SIGS_OPTIM}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = i64 if name.endswith(("_work_floats", "_split_floats", "_work_ints")) else i32

@@ -206,6 +206,131 @@ extern "C" int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long
     return EGO_OK;
 }
 
+// ---- parameter-group AdamW: every (layer, weight-decay class) group of a layer-wise lr decay in ONE launch ---------------------
+//
+// Replaces: the per-group loop of torch.optim.AdamW over the groups get_parameter_groups builds (egom2p/utils/optim_factory.py:97-154,
+// 226), each at lr * lr_scale (run_training_egom2p.py:707-713).  The flat buffers are cut into segments (contiguous runs of one
+// group, one step offset, frozen or not); work is dealt in chunks of EGO_ADAMW_CHUNK floats that never cross a segment, and a
+// workgroup finds its chunk's segment by binary search on the segments' first-chunk prefix array.
+namespace {
+
+constexpr int SEG_CHUNK = EGO_ADAMW_CHUNK;          // 256 threads x f32x4 x 4
+static_assert(SEG_CHUNK == 256 * 4 * 4, "a chunk is four f32x4 per thread of a 256-thread workgroup");
+
+// the per-element expression is adamw_kernel's, term for term, with the three multiply-adds the compiler fuses THERE written as
+// fmaf here (decay, the two moments, the parameter update) and contraction switched off for the rest: left to itself the compiler
+// fuses the four unrolled copies of this loop differently from adamw_kernel's one, and the two paths would differ in the last bit.
+// Everything a workgroup decides (segment, group, frozen, gated) is uniform over it: the table loads are read-only and indexed by
+// blockIdx / loop counters alone.
+__global__ __launch_bounds__(256) void adamw_seg_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long n, const ego_adamw_seg* __restrict__ segs,
+                                                        int n_segs, const long* __restrict__ chunks, long n_chunks,
+                                                        const ego_adamw_hp hp, float b1, float b2, float eps, float gscale,
+                                                        float max_norm, const double* __restrict__ sqnorm, int zero_grad,
+                                                        const int* __restrict__ gate) {
+#pragma clang fp contract(off)
+    __shared__ float s_bc1[EGO_ADAMW_MAX_GROUPS], s_bc2[EGO_ADAMW_MAX_GROUPS];
+    const int gated = gate ? gate[0] : 0;
+    if (gated && !zero_grad) return;
+    if (!gated && threadIdx.x < EGO_ADAMW_MAX_GROUPS) {
+        const int k = threadIdx.x;
+        float bc1 = hp.bc1[k], bc2 = hp.bc2_sqrt[k];
+        if (gate && k < hp.n_groups) {             // adamw_gated_kernel's count and corrections, once per group and workgroup
+            int t = hp.step[k] - gate[1];
+            if (t < 1) t = 1;
+            bc1 = (float)(1.0 - pow((double)b1, (double)t));
+            bc2 = (float)sqrt(1.0 - pow((double)b2, (double)t));
+        }
+        s_bc1[k] = bc1;
+        s_bc2[k] = bc2;
+    }
+    __syncthreads();
+    float coef = gscale;
+    if (max_norm > 0.f && sqnorm) {
+        coef *= fminf(1.f, max_norm / fmaf((float)sqrt(*sqnorm), gscale, 1e-6f));       // (total + 1e-6f, fused as adamw_kernel's is)
+    }
+    for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        int a = 0, b = n_segs - 1;                  // the last segment whose first chunk is <= c
+        while (a < b) {
+            const int mid = (a + b + 1) >> 1;
+            if (chunks[mid] <= c) a = mid; else b = mid - 1;
+        }
+        const ego_adamw_seg sg = segs[a];
+        const long lo = sg.lo + (c - chunks[a]) * SEG_CHUNK;
+        const long hi = lo + SEG_CHUNK < sg.hi ? lo + SEG_CHUNK : sg.hi;
+        const int grp = __builtin_amdgcn_readfirstlane(sg.group);
+        // (a table that does not fit the buffers or the block is the caller's error - the entry point checks its host copy -
+        //  but nothing outside [0, n) or the block is touched even then)
+        if (sg.lo < 0 || sg.hi > n || lo < sg.lo || (unsigned)grp >= (unsigned)EGO_ADAMW_MAX_GROUPS) continue;
+        if (gated || (sg.flags & EGO_SEG_FROZEN)) {
+            if (zero_grad)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+                    if (i < hi) *(f32x4*)(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            continue;
+        }
+        const float lr = hp.lr[grp], wd = hp.wd[grp], bc1 = s_bc1[grp], bc2_sqrt = s_bc2[grp];
+        const float step = lr / bc1, decay = fmaf(-lr, wd, 1.f);
+        f32x4 pp[4], gg[4], mm[4], vv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+            if (i < hi) { pp[k] = *(f32x4*)(p + i); gg[k] = *(f32x4*)(g + i); mm[k] = *(f32x4*)(m + i); vv[k] = *(f32x4*)(v + i); }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+            if (i >= hi) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ge = gg[k][e] * coef;
+                mm[k][e] = fmaf(b1, mm[k][e], (1.f - b1) * ge);
+                vv[k][e] = fmaf(b2, vv[k][e], (1.f - b2) * ge * ge);
+                pp[k][e] = fmaf(decay, pp[k][e], -(step * (mm[k][e] / (sqrtf(vv[k][e]) / bc2_sqrt + eps))));
+            }
+            *(f32x4*)(p + i) = pp[k]; *(f32x4*)(m + i) = mm[k]; *(f32x4*)(v + i) = vv[k];
+            if (zero_grad) *(f32x4*)(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int ego_adamw_step_seg(float* p, float* g, float* m, float* v, long n, const ego_adamw_seg* segs_host,
+                                  const ego_adamw_seg* segs, int n_segs, const long* chunks, const ego_adamw_hp* hp, float beta1,
+                                  float beta2, float eps, float gscale, float max_norm, const double* sqnorm, int zero_grad,
+                                  const int* gate, hipStream_t stream) {
+    if (n_segs < 0 || n < 0 || !hp || hp->n_groups < 0 || hp->n_groups > EGO_ADAMW_MAX_GROUPS) return EGO_ERR_ARG;
+    if (((uintptr_t)p) % 16 || ((uintptr_t)g) % 16 || ((uintptr_t)m) % 16 || ((uintptr_t)v) % 16 || ((uintptr_t)gate) % 4 ||
+        ((uintptr_t)sqnorm) % 8)
+        return EGO_ERR_ARG;
+    if (n_segs == 0) return EGO_OK;
+    if (!p || !g || !m || !v || !segs_host || !segs || !chunks || ((uintptr_t)segs) % 8 || ((uintptr_t)chunks) % 8) return EGO_ERR_ARG;
+    long n_chunks = 0, prev = 0;
+    for (int s = 0; s < n_segs; ++s) {
+        const ego_adamw_seg& sg = segs_host[s];
+        if (sg.lo < prev || sg.hi <= sg.lo || sg.hi > n || (sg.lo & 3) || (sg.hi & 3)) return EGO_ERR_ARG;
+        if (sg.group < 0 || sg.group >= hp->n_groups) return EGO_ERR_ARG;
+        if (!(sg.flags & EGO_SEG_FROZEN) && hp->step[sg.group] < 1) return EGO_ERR_ARG;
+        prev = sg.hi;
+        n_chunks += (sg.hi - sg.lo + SEG_CHUNK - 1) / SEG_CHUNK;
+    }
+    ego_adamw_hp h = *hp;                           // passed by value: the launch owns its copy, the caller may rewrite its block
+    if (!gate)
+        for (int k = 0; k < h.n_groups; ++k) {      // as ego_adamw_step forms them
+            const int t = h.step[k] < 1 ? 1 : h.step[k];
+            h.bc1[k] = (float)(1.0 - pow((double)beta1, (double)t));
+            h.bc2_sqrt[k] = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+        }
+    const int blocks = (int)(n_chunks < 4096 ? n_chunks : 4096);
+    EGO_LAUNCH(adamw_seg_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, segs, n_segs, chunks, n_chunks, h, beta1,
+                       beta2, eps, gscale, max_norm, sqnorm, zero_grad, gate);
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
 // ---- model EMA: a moving average of the flat parameter buffer, and the in-place exchange that applies it ---------------------
 //
 // Replaces: ModelEmaV2.update (egom2p/utils/timm/model_ema.py:128-132: `ema_v.copy_(decay * ema_v + (1 - decay) * model_v)` per

@@ -435,6 +435,59 @@ def adamw_step_gated(p, g, m, v, lr, wd, step, gate, beta1=0.9, beta2=0.95, eps=
                                         _p(sqnorm), int(zero_grad), _p(gate), _stream()), "ego_adamw_step_gated")
 
 
+def seg_chunks(segs):
+    """First chunk of every segment (lo, hi, group, flags), and the total: work is dealt in chunks of L.ADAMW_CHUNK floats that
+    never cross a segment.  Pure host arithmetic."""
+    first, total = [], 0
+    for lo, hi, _, _ in segs:
+        first.append(total)
+        total += (hi - lo + L.ADAMW_CHUNK - 1) // L.ADAMW_CHUNK
+    return first, total
+
+
+class AdamwSegTable:
+    """The static half of `adamw_step_seg`: the segment table in host memory and on the device, and the chunk prefix array.
+    Built when the grouping or the frozen set changes, never per step."""
+
+    def __init__(self, segs, device):
+        segs = [(int(lo), int(hi), int(grp), int(fl)) for lo, hi, grp, fl in segs]
+        prev = 0
+        for lo, hi, grp, fl in segs:
+            if lo < prev or hi <= lo or lo % 4 or hi % 4 or not 0 <= grp < L.ADAMW_MAX_GROUPS:
+                raise L.EgoHipError(f"adamw segment table: segment ({lo}, {hi}, group {grp}) is out of order, empty, not a multiple of 4 "
+                                    "or names a group outside the block")
+            prev = hi
+        self.segs = segs
+        self.host = (L.AdamwSeg * max(len(segs), 1))(*[L.AdamwSeg(*s) for s in segs])
+        first, self.n_chunks = seg_chunks(segs)
+        raw = torch.frombuffer(bytearray(bytes(self.host)), dtype=torch.uint8) if segs else torch.zeros(C.sizeof(L.AdamwSeg), dtype=torch.uint8)
+        self.dev = raw.to(device)
+        self.chunks = torch.tensor(first or [0], dtype=torch.int64).to(device)
+        self.elems_active = sum(hi - lo for lo, hi, _, fl in segs if not fl & L.SEG_FROZEN)
+        self.elems_frozen = sum(hi - lo for lo, hi, _, fl in segs if fl & L.SEG_FROZEN)
+
+    def __len__(self):
+        return len(self.segs)
+
+
+def adamw_step_seg(p, g, m, v, table, hp, beta1=0.9, beta2=0.95, eps=1e-8, gscale=1.0, max_norm=0.0, sqnorm=None, zero_grad=False,
+                   gate=None):
+    """One launch over the flat buffers: every segment of `table` (AdamwSegTable) steps with the (lr, wd, step) of its slot in
+    `hp` - a sequence of at most L.ADAMW_MAX_GROUPS triples, copied into the kernel arguments.  gate: as `adamw_step_gated`."""
+    _need_cuda(p, g, m, v, table.dev, table.chunks)
+    if gate is not None and (gate.dtype != torch.int32 or gate.numel() < GATE_WORDS):
+        raise L.EgoHipError("adamw_step_seg: gate must hold GATE_WORDS int32")
+    if len(hp) > L.ADAMW_MAX_GROUPS:
+        raise L.EgoHipError(f"adamw_step_seg: {len(hp)} hyper-parameter slots, the block holds {L.ADAMW_MAX_GROUPS}")
+    blk = L.AdamwHp()
+    blk.n_groups = len(hp)
+    for k, (lr, wd, step) in enumerate(hp):
+        blk.lr[k], blk.wd[k], blk.step[k] = lr, wd, int(step)
+    check(L.load().ego_adamw_step_seg(_p(p), _p(g), _p(m), _p(v), p.numel(), table.host, _p(table.dev), len(table), _p(table.chunks),
+                                      C.byref(blk), beta1, beta2, eps, gscale, max_norm, _p(sqnorm), int(zero_grad), _p(gate),
+                                      _stream()), "ego_adamw_step_seg")
+
+
 def _flat_f32(name, *ts):
     _need_cuda(*ts)
     for t in ts:

@@ -21,12 +21,121 @@ def is_no_decay(name: str, skip_list=()) -> bool:
     return "norm." in name or ".norm" in name or name.endswith(".bias") or name in skip_list
 
 
+def get_num_layer_for_fm(var_name: str, num_enc_layers: int, num_dec_layers: int, last_layer_mod_emb: bool = False) -> int:
+    """Layer id of a parameter for layer-wise lr decay (optim_factory.py:62-79): 0 = the encoder embeddings, i + 1 = encoder block
+    i, num_enc + j + 1 = decoder block j, num_enc + num_dec + 1 = everything behind the decoder.
+
+    Restated as the reference BEHAVES on real parameter names, not as its docstring reads: it compares the whole name with
+    ("encoder_norm", "decoder_proj_context", "mask_token"), so `encoder_norm.weight`, `decoder_proj_context.weight` and
+    `decoder_proj_context.bias` never match and fall through to the LAST layer id; only `mask_token` (a bare name) gets
+    num_enc.  `register_tokens` and the decoder embeddings' tables fall through as well.  Kept on purpose: a model fine-tuned here
+    takes the lr scales it would take there."""
+    if var_name.startswith("encoder_embeddings"):
+        return 0
+    if var_name.startswith("encoder."):
+        return int(var_name.split(".")[1]) + 1
+    if var_name in ("encoder_norm", "decoder_proj_context", "mask_token"):
+        return num_enc_layers
+    if not last_layer_mod_emb and var_name.startswith("decoder_embeddings.") and "mod_emb" in var_name:
+        return num_enc_layers
+    if var_name.startswith("decoder."):
+        return num_enc_layers + int(var_name.split(".")[1]) + 1
+    return num_enc_layers + num_dec_layers + 1
+
+
+class LayerDecayValueAssigner:
+    """optim_factory.py:82-88: `values[layer_id]` is the layer's lr scale."""
+
+    def __init__(self, values):
+        self.values = list(values)
+
+    def get_scale(self, layer_id: int) -> float:
+        return self.values[layer_id]
+
+
+def layer_decay_values(layer_decay: float, num_layers: int) -> List[float]:
+    """The scales of `--layer_decay`: layer_decay ** (L + 1 - i) for i in 0 .. L + 1 (the last layer id has scale 1)."""
+    return [layer_decay ** (num_layers + 1 - i) for i in range(num_layers + 2)]
+
+
+def get_parameter_groups(model, weight_decay=1e-5, skip_list=(), get_num_layer=None, get_layer_scale=None, decoder_decay=None,
+                         decoder_list=(), no_lr_scale_list=()):
+    """The groups of optim_factory.py:97-154, in the order of first appearance: one per (layer id, weight-decay class), named
+    `layer_%d_{decay,no_decay,decoder_decay}[_no_lr_scale]` (without a layer function: the bare class).  A group's lr_scale is the
+    layer's (1.0 without a scale function and for `no_lr_scale_list` names).  Tensors with requires_grad=False are left out.
+    Every group also lists its parameters' names (`param_names`), which the flat-buffer optimiser needs."""
+    groups: Dict[str, Dict] = {}
+    for name, param in model.named_parameters():
+        name = name.replace("_fsdp_wrapped_module.", "")
+        if not param.requires_grad:
+            continue
+        if is_no_decay(name, skip_list) or name.endswith((".lookup_table_weight", ".gamma")):
+            cls, wd = "no_decay", 0.0
+        elif decoder_decay is not None and (name.startswith("decoder.") or name in decoder_list):
+            cls, wd = "decoder_decay", decoder_decay
+        else:
+            cls, wd = "decay", weight_decay
+        layer_id, unscaled = None, False
+        if get_num_layer is not None:
+            layer_id = get_num_layer(name)
+            cls = "layer_%d_%s" % (layer_id, cls)
+            if name in no_lr_scale_list:
+                unscaled = True
+                cls += "_no_lr_scale"
+        if cls not in groups:
+            scale = get_layer_scale(layer_id) if get_layer_scale is not None and not unscaled else 1.0
+            groups[cls] = {"name": cls, "weight_decay": wd, "params": [], "param_names": [], "lr_scale": scale}
+        groups[cls]["params"].append(param)
+        groups[cls]["param_names"].append(name)
+    return list(groups.values())
+
+
+def build_segments(offsets, never_grad, group_of, skipped, frozen):
+    """Pure host logic of the segmented step.  offsets: engine key -> (offset, numel, shape) in flat order; group_of: engine key ->
+    group index (a tensor in no group never steps); skipped: key -> optimiser steps the tensor sat out; frozen: keys that sit this
+    phase out.  Returns segments (lo, hi, group, step offset, frozen): every tensor outside `never_grad` is covered exactly (padded
+    to 4 floats, as the engine lays it out), ascending; neighbours merge only when they touch and agree in (group, offset, frozen)."""
+    segs: List[List] = []
+    for name, (o, n, _) in offsets.items():
+        if name in never_grad:
+            continue
+        n4 = (n + 3) // 4 * 4
+        fro = name in frozen or name not in group_of
+        key = (0, 0, True) if fro else (group_of[name], skipped.get(name, 0), False)
+        if segs and segs[-1][1] == o and tuple(segs[-1][2:]) == key:
+            segs[-1][1] = o + n4
+        else:
+            segs.append([o, o + n4, *key])
+    return [tuple(s) for s in segs]
+
+
+def plan_launches(segments, max_groups: int = 128):
+    """Segments -> launches: [(table rows (lo, hi, slot, flags), slots [(group, step offset), ...])].  A launch holds at most
+    `max_groups` distinct (group, step offset) combinations - the kernel's hyper-parameter block; a frozen segment takes slot 0."""
+    launches, rows, slots = [], [], {}
+    for lo, hi, grp, sk, fro in segments:
+        if not fro and (grp, sk) not in slots and len(slots) == max_groups:
+            launches.append((rows, list(slots)))
+            rows, slots = [], {}
+        if fro:
+            rows.append((lo, hi, 0, 1))
+        else:
+            rows.append((lo, hi, slots.setdefault((grp, sk), len(slots)), 0))
+    if rows:
+        launches.append((rows, list(slots)))
+    return launches
+
+
 class FusedAdamW:
     """Duck-types the torch optimiser surface the reference loop touches: `param_groups` (with "lr",
-    "weight_decay", "lr_scale"), `step`, `zero_grad`, `state_dict`, `load_state_dict`."""
+    "weight_decay", "lr_scale"), `step`, `zero_grad`, `state_dict`, `load_state_dict`.
+
+    `param_groups` (optional): the groups of `get_parameter_groups` - any number, each with its own weight decay and lr_scale.
+    Without it the optimiser has the two groups `decay` / `no_decay` and steps one launch per run of equal weight-decay class;
+    with it every group, step offset and frozen range is a segment of ONE `ops.adamw_step_seg` launch."""
 
     def __init__(self, engine, lr: float = 1e-4, weight_decay: float = 0.05, betas=(0.9, 0.95), eps: float = 1e-8,
-                 named_parameters=None, world_size: int = 1):
+                 named_parameters=None, world_size: int = 1, param_groups=None):
         self.engine = engine
         self.betas, self.eps = betas, eps
         self.world_size = world_size
@@ -42,6 +151,28 @@ class FusedAdamW:
             {"params": decay, "weight_decay": weight_decay, "lr": lr, "lr_scale": 1.0, "name": "decay"},
             {"params": nodecay, "weight_decay": 0.0, "lr": lr, "lr_scale": 1.0, "name": "no_decay"},
         ]
+        self.segmented = param_groups is not None
+        self._launches: List = []                  # segmented path: [(ops.AdamwSegTable, [(group index, step offset), ...])]
+        if self.segmented:
+            if not named:
+                raise ValueError("FusedAdamW: parameter groups need named_parameters (tensors are placed by name)")
+            name_of = {id(p): n for n, p in named}
+            self.param_groups, self._group_of = [], {}
+            for gi, src in enumerate(param_groups):
+                names = list(src.get("param_names") or [name_of[id(p)] for p in src["params"]])
+                grp = {"params": list(src["params"]), "param_names": names, "weight_decay": float(src.get("weight_decay", weight_decay)),
+                       "lr": float(src.get("lr", lr)), "lr_scale": float(src.get("lr_scale", 1.0)), "name": src.get("name", f"group_{gi}")}
+                self.param_groups.append(grp)
+                for n in names:
+                    key = engine._canon_key(n)
+                    if key not in engine.offsets:
+                        raise ValueError(f"FusedAdamW: parameter '{n}' of group '{grp['name']}' is not a tensor of this engine")
+                    if self._group_of.setdefault(key, gi) != gi:
+                        raise ValueError(f"FusedAdamW: parameter '{n}' is in two groups")
+            known = {engine._canon_key(n) for n, _ in named} | set(engine.never_grad)
+            stray = [k for k in engine.offsets if k not in known]
+            if stray:
+                raise ValueError(f"FusedAdamW: engine tensors without a named parameter: {stray[:4]}")
         self._frozen_sig = None
         self._runs = [(lo, hi, nd, 0) for lo, hi, nd in engine.opt_runs]
         self._frozen_ranges: List = []          # [lo, hi) ranges of the flat buffers that belong to frozen tensors
@@ -108,6 +239,27 @@ class FusedAdamW:
                 self._frozen_names = [n for n in fnames if n not in eng.never_grad]
         return self._runs
 
+    def segments(self):
+        """The segmented path's (lo, hi, group, step offset, frozen) runs for the present frozen set and step offsets."""
+        eng = self.engine
+        frozen = {eng._canon_key(n) for n, p in self._named if not p.requires_grad}
+        return build_segments(eng.offsets, eng.never_grad, self._group_of, self.skipped, frozen)
+
+    def _plan(self):
+        """Segment tables of the segmented path, rebuilt (and uploaded) only when the frozen signature changes."""
+        sig = tuple(p.requires_grad for _, p in self._named)
+        if sig != self._frozen_sig:
+            self._fold_gated()                      # with the OLD frozen names, before the segments take their step offsets
+            self._frozen_sig = sig
+            segs = self.segments()
+            self._launches = [(ops.AdamwSegTable(rows, self.engine.dev), slots) for rows, slots in plan_launches(segs, ops.L.ADAMW_MAX_GROUPS)]
+            self._runs = [(lo, hi, grp, sk) for lo, hi, grp, sk, fro in segs if not fro]
+            self._frozen_ranges = [(lo, hi) for lo, hi, _, _, fro in segs if fro]
+            eng = self.engine
+            frozen = {eng._canon_key(n) for n, p in self._named if not p.requires_grad}
+            self._frozen_names = [k for k in eng.offsets if k in frozen and k in self._group_of and k not in eng.never_grad]
+        return self._launches
+
     @torch.no_grad()
     def step(self, clip_grad: Optional[float] = None, zero_grad: bool = True, skip_grad: Optional[float] = None,
              skip_nonfinite: bool = False):
@@ -127,7 +279,8 @@ class FusedAdamW:
         self.t += 1
         gscale = 1.0 / self.world_size
         norm = None
-        runs = self._active_runs()
+        launches = self._plan() if self.segmented else None
+        runs = self._runs if self.segmented else self._active_runs()
         if clip_grad is not None or gated:
             # clip_grad_norm_ of the reference (native_scaler.py:33) sees only tensors that have a gradient: the engine's
             # backward writes every tensor's gradient, so frozen ranges are left out of the norm here
@@ -144,12 +297,24 @@ class FusedAdamW:
             ops.adamw_gate(self.sqnorm, self.gate, gscale=gscale, skip_norm=float(skip_grad) if skip_grad is not None else 0.0,
                            skip_nonfinite=skip_nonfinite)
             self._gate_pending = True
-        if zero_grad:
+        if zero_grad and not self.segmented:
             for lo, hi in self._frozen_ranges:      # never consumed: must not accumulate from step to step
                 eng.G[lo:hi].zero_()
-        decay, nodecay = self.param_groups
         for name in self._frozen_names:             # this step passes them by, as torch's per-parameter step counter would
             self.skipped[name] = self.skipped.get(name, 0) + 1
+        if self.segmented:
+            # one launch (or the few the block's 128 slots force): frozen ranges are segments too, their gradients zeroed in-kernel
+            for table, slots in launches:
+                hp = [(float(self.param_groups[gi]["lr"]), float(self.param_groups[gi]["weight_decay"]), self.t - sk)
+                      for gi, sk in slots] or [(0.0, 0.0, 1)]
+                ops.adamw_step_seg(eng.P, eng.G, self.m, self.v, table, hp, self.betas[0], self.betas[1], self.eps, gscale=gscale,
+                                   max_norm=float(clip_grad) if clip_grad else 0.0,
+                                   sqnorm=self.sqnorm if (clip_grad or gated) else None, zero_grad=zero_grad,
+                                   gate=self.gate if gated else None)
+            eng.weights_dirty = True
+            self.last_grad_norm = norm
+            return norm
+        decay, nodecay = self.param_groups
         for lo, hi, nd, sk in runs:
             grp = nodecay if nd else decay
             if gated:
@@ -175,7 +340,7 @@ class FusedAdamW:
         self._fold_gated()                          # `t` and `skipped` leave as applied-step counts
         return {"m": self.m, "v": self.v, "t": self.t, "skipped": dict(self.skipped), "layout": self.engine.layout_tag(),
                 "gated_total": self.gated_total(),
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+                "param_groups": [{k: v for k, v in g.items() if k not in ("params", "param_names")} for g in self.param_groups]}
 
     def load_state_dict(self, sd):
         have, want = sd.get("layout"), self.engine.layout_tag()
@@ -201,6 +366,11 @@ class FusedAdamW:
                                "or restart the optimizer state")
         if sd["m"].numel() != self.m.numel():
             raise RuntimeError(f"optimizer state has {sd['m'].numel()} moments, this engine {self.m.numel()} parameters")
+        saved, mine = [s.get("name") for s in sd["param_groups"]], [g["name"] for g in self.param_groups]
+        if saved != mine:
+            raise RuntimeError(f"optimizer state was saved with the parameter groups {saved[:4]}{'...' if len(saved) > 4 else ''} "
+                               f"({len(saved)}), this optimiser has {mine[:4]}{'...' if len(mine) > 4 else ''} ({len(mine)}): build it "
+                               "with the same layer_decay / decoder_decay / no_lr_scale_list, or restart the optimizer state")
         self.m.copy_(sd["m"]); self.v.copy_(sd["v"]); self.t = int(sd["t"])
         self.skipped = {str(k): int(v) for k, v in sd.get("skipped", {}).items()}
         # the restored counts are folded ones: whatever this optimiser's device block counted belongs to the state it replaces
@@ -213,15 +383,35 @@ class FusedAdamW:
             g.update(s)
 
 
-def create_optimizer(args, model, **_):
-    """`create_optimizer(args, model_without_ddp)` of the reference (optim_factory.py:157-230), AdamW only."""
+def create_optimizer(args, model, get_num_layer=None, get_layer_scale=None, filter_bias_and_bn=True, skip_list=None):
+    """`create_optimizer` of the reference (optim_factory.py:157-230), AdamW only.  `get_num_layer` (name -> layer id) and
+    `get_layer_scale` (layer id -> lr scale) give layer-wise lr decay; `args.decoder_decay` (a weight decay of its own for names
+    starting `decoder.`) and `args.no_lr_scale_list` ("a-b-c": names that keep scale 1) are read as the reference reads them
+    (:163-170).  With none of them the optimiser is the two-group one on its per-run launches."""
     if getattr(args, "opt", "adamw").lower().split("_")[-1] != "adamw":
         raise NotImplementedError("only AdamW is on the accelerated path")
     betas = tuple(args.opt_betas) if getattr(args, "opt_betas", None) else (0.9, 0.999)
     eps = args.opt_eps if getattr(args, "opt_eps", None) else 1e-8
     world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+    decoder_decay = getattr(args, "decoder_decay", None)
+    no_lr_scale = getattr(args, "no_lr_scale_list", None)
+    no_lr_scale = no_lr_scale.split("-") if isinstance(no_lr_scale, str) else []
+    groups = None
+    if not (args.weight_decay and filter_bias_and_bn):
+        if get_num_layer is not None or get_layer_scale is not None or decoder_decay is not None:
+            # (the reference hands AdamW the bare parameter list here, :183-186, and the layer functions are silently dropped)
+            raise ValueError("layer-wise lr decay / decoder_decay need weight_decay > 0 and filter_bias_and_bn=True: "
+                             "the reference builds no parameter groups otherwise")
+        if not filter_bias_and_bn:                 # (:184-186: one group, the weight decay on every tensor)
+            kept = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+            groups = [{"name": "all", "params": [p for _, p in kept], "param_names": [n for n, _ in kept],
+                       "weight_decay": args.weight_decay, "lr_scale": 1.0}]
+    elif get_num_layer is not None or get_layer_scale is not None or decoder_decay is not None or skip_list:
+        skip = skip_list if skip_list is not None else (model.no_weight_decay() if hasattr(model, "no_weight_decay") else ())
+        dec = model.decoder_weight_decay() if hasattr(model, "decoder_weight_decay") else ()
+        groups = get_parameter_groups(model, args.weight_decay, skip, get_num_layer, get_layer_scale, decoder_decay, dec, no_lr_scale)
     return FusedAdamW(model.engine, lr=args.lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
-                      named_parameters=model.named_parameters(), world_size=world)
+                      named_parameters=model.named_parameters(), world_size=world, param_groups=groups)
 
 
 class NativeScalerWithGradNormCount:

@@ -175,6 +175,9 @@ class KernelTimer:
         def c_adamw(p, g, m, v, *a, zero_grad=False, **kw):
             return 0.0, float(p.numel()) * (16 + 12 + (4 if zero_grad else 0))
 
+        def c_adamw_seg(p, g, m, v, table, hp, *a, **kw):
+            return 0.0, 28.0 * table.elems_active + 4.0 * table.elems_frozen      # p, m, v read and written, g read and zeroed | g zeroed
+
         def c_ema_update(ema, p, decay):
             return 0.0, float(ema.numel()) * 12.0                       # p and ema read, ema written
 
@@ -193,7 +196,8 @@ class KernelTimer:
         other = {"droppath_draw": c_droppath_draw, "droppath_resid": c_droppath_resid, "droppath_scale": c_droppath_scale,
                  "compact": c_compact, "embed_fwd": c_embed_fwd, "embed_bwd": c_embed_bwd, "loss_perm": c_loss_perm,
                  "loss_finalize": c_loss_finalize, "cast_weight": c_cast_weight, "cast_f32_bf16": c_cast, "bias_grad": c_bias_grad,
-                 "grad_sqnorm": c_sqnorm, "adamw_step": c_adamw, "ema_update": c_ema_update, "swap_f32": c_swap}
+                 "grad_sqnorm": c_sqnorm, "adamw_step": c_adamw, "adamw_step_seg": c_adamw_seg,
+                 "ema_update": c_ema_update, "swap_f32": c_swap}
         self.cost_table = dict(table, **other)
         saved = {}
         # the fused launches are the same device kernel (gemm_nt256_kernel<EK>) behind other entry points: one class

@@ -24,6 +24,7 @@ import os
 import random
 import sys
 import time
+from functools import partial
 
 import numpy as np
 import torch
@@ -37,7 +38,8 @@ from egom2p_amd.config import MODALITIES, MODEL_CFGS, ModelCfg  # noqa: E402
 from egom2p_amd.dp import DataParallel, init_distributed_mode  # noqa: E402
 from egom2p_amd.ema import ModelEma  # noqa: E402
 from egom2p_amd.model import MODALITY_INFO, create_model  # noqa: E402
-from egom2p_amd.optim import NativeScalerWithGradNormCount, create_optimizer  # noqa: E402
+from egom2p_amd.optim import (LayerDecayValueAssigner, NativeScalerWithGradNormCount, create_optimizer,  # noqa: E402
+                              get_num_layer_for_fm, layer_decay_values)
 from egom2p_amd.scheduler import build_schedules  # noqa: E402
 
 
@@ -86,6 +88,12 @@ def get_args(argv=None):
                    help="decay of update k is min(decay, (1 + k) / (10 + k)): a short run does not keep its initial weights")
     p.add_argument("--weight_decay", default=0.05, type=float)
     p.add_argument("--weight_decay_end", default=None, type=float, help="final weight decay (default: constant)")
+    p.add_argument("--layer_decay", default=None, type=float,
+                   help="layer-wise lr decay: layer i of L + 2 trains at lr * F ** (L + 1 - i), L = encoder + decoder depth "
+                        "(default: none).  The reference's create_optimizer accepts the layer functions, its script never passes them")
+    p.add_argument("--decoder_decay", default=None, type=float, help="weight decay of the decoder blocks' matrices (default: --weight_decay)")
+    p.add_argument("--no_lr_scale_list", default="", type=str, help="'-'-joined parameter names that keep lr scale 1 under --layer_decay")
+    p.add_argument("--finetune", default="", help="start from the `model` weights of a local checkpoint (no optimiser state, no epoch)")
     p.add_argument("--blr", default=1e-4, type=float, help="base lr: lr = blr * global_batch / 256")
     p.add_argument("--min_blr", default=0.0, type=float)
     p.add_argument("--frozen_model_blr", default=-1, type=float, help="base lr of the frozen-model phase (default: blr)")
@@ -242,7 +250,9 @@ def train_one_epoch(model, loader, optimizer, scaler, args, epoch, start_steps, 
             print(f"Epoch: [{epoch}] step {step} loss {lv:.4f} " + " ".join(f"{m}_loss {v.item():.3f}" for m, v in mod_loss.items()) +
                   f" grad_norm {gn_txt} lr {optimizer.param_groups[0]['lr']:.3e} wd {optimizer.param_groups[0]['weight_decay']:.4f} "
                   f"clips/s/gpu {seen / max(dt, 1e-9):.1f}" +
-                  (f" gated_steps {optimizer.gated_total()}" if gating else ""), flush=True)
+                  (f" gated_steps {optimizer.gated_total()}" if gating else "") +
+                  (" group_lrs " + " ".join(f"{g['name']}={g['lr']:.3e}" for g in optimizer.param_groups)
+                   if getattr(optimizer, "segmented", False) else ""), flush=True)
         if args.max_steps > 0 and step + 1 >= args.max_steps:
             break
     torch.cuda.synchronize()
@@ -310,6 +320,18 @@ def load_checkpoint(ck, model, optimizer=None, model_ema=None):
     return int(ck.get("epoch", -1)) + 1
 
 
+def load_finetune(path, model):
+    """reference :477-489: the `model` weights of a checkpoint minus every `.pos_emb` key, loaded non-strictly; no optimiser state,
+    no epoch.  Local files only, read with weights_only=True (the reference also fetches https URLs through torch.hub)."""
+    if str(path).startswith(("https:", "http:")):
+        raise ValueError("--finetune takes a local checkpoint file: fetch the weights yourself and pass the path")
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    msg = model.load_state_dict({k: v for k, v in ck["model"].items() if ".pos_emb" not in k}, strict=False)
+    # (the fixed positional tables are buffers of every model here: dropping them always lists them as missing)
+    print(f"finetune {path}: missing keys {list(msg.missing_keys)} unexpected keys {list(msg.unexpected_keys)}", flush=True)
+    return msg
+
+
 def main(args):
     distributed = init_distributed_mode(args)
     rank = args.rank if distributed else 0
@@ -320,8 +342,19 @@ def main(args):
     model = get_model(args)
     global_batch = args.batch_size * args.accum_iter * world
     args.lr = args.blr * global_batch / 256                      # reference :498-505
+    if args.finetune:
+        load_finetune(args.finetune, model)
     model = DataParallel(model)
-    optimizer = create_optimizer(args, model.module)
+    layer_fn = scale_fn = None
+    if args.layer_decay is not None:
+        # the reference's plumbing (optim_factory.py:62-88, 123-138) wired to a switch of this script: its own never passes them
+        depth_e, depth_d = model.module.get_num_layers_encoder(), model.module.get_num_layers_decoder()
+        layer_fn = partial(get_num_layer_for_fm, num_enc_layers=depth_e, num_dec_layers=depth_d)
+        scale_fn = LayerDecayValueAssigner(layer_decay_values(args.layer_decay, depth_e + depth_d)).get_scale
+    optimizer = create_optimizer(args, model.module, get_num_layer=layer_fn, get_layer_scale=scale_fn)
+    if rank == 0 and optimizer.segmented:
+        print("Param groups: " + ", ".join(f"{g['name']} lr_scale {g['lr_scale']:.4f} wd {g['weight_decay']:g} ({len(g['params'])})"
+                                           for g in optimizer.param_groups), flush=True)
     # (every rank keeps its own average: the ranks' parameters are bitwise equal after every step, so the averages are too)
     model_ema = ModelEma(model.module, decay=args.model_ema_decay, warmup=args.model_ema_warmup) if args.model_ema else None
     scaler = NativeScalerWithGradNormCount(enabled=False, skip_nonfinite=args.skip_nonfinite_grad)   # bf16: GradScaler disabled (:518)
