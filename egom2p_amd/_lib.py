@@ -175,6 +175,13 @@ _SIGS_OPTIM = {
                            vp, vp],
 }
 EXPORTS_OPTIM = tuple(_SIGS_OPTIM)
+
+# include/egom2p_hip_optim_kinds.h: Adam / SGD / Nesterov on the segmented launch (tests/test_optim_kinds_cpu.py holds header and table)
+OPT_ADAM, OPT_SGD, OPT_NESTEROV = 1, 2, 3                  # EGO_OPT_ADAM, EGO_OPT_SGD, EGO_OPT_NESTEROV
+_SIGS_OPTIM_KINDS = {
+    "ego_optim_step_seg": _SIGS_OPTIM["ego_adamw_step_seg"][:-1] + [i32, f32, vp],
+}
+EXPORTS_OPTIM_KINDS = tuple(_SIGS_OPTIM_KINDS)
 _lib = None
 
 
@@ -197,7 +204,7 @@ def load():
         if os.path.exists(hip_rt):
             C.CDLL(hip_rt, mode=C.RTLD_GLOBAL)
         lib = C.CDLL(LIB_PATH)
-        for name, args in {**_SIGS, **_SIGS_OPTIM}.items():
+        for name, args in {**_SIGS, **_SIGS_OPTIM, **_SIGS_OPTIM_KINDS}.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = i64 if name.endswith(("_work_floats", "_split_floats", "_work_ints")) else i32

@@ -331,6 +331,154 @@ extern "C" int ego_adamw_step_seg(float* p, float* g, float* m, float* v, long n
     return EGO_OK;
 }
 
+// ---- Adam, SGD with momentum and Nesterov on the segmented launch ---------------------------------------------------------------
+//
+// Replaces: optim.SGD(momentum, nesterov=True / False) and optim.Adam of create_optimizer (egom2p/utils/optim_factory.py:217-224),
+// looped over the groups of :97-154.  adamw_seg_kernel's frame - chunks that never cross a segment, the segment found by binary
+// search, everything a workgroup decides uniform over it - with the optimiser kind a template parameter: the SGD kinds carry
+// no `v` traffic (20 B per element with zero_grad against 28) and no bias-correction prologue.
+namespace {
+
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_seg_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long n, const ego_adamw_seg* __restrict__ segs,
+                                                        int n_segs, const long* __restrict__ chunks, long n_chunks,
+                                                        const ego_adamw_hp hp, float b1, float b2, float eps, float momentum,
+                                                        float gscale, float max_norm, const double* __restrict__ sqnorm,
+                                                        int zero_grad, const int* __restrict__ gate) {
+    // every multiply-add is written out as fmaf and contraction is off for the rest (as in adamw_seg_kernel): the rounding points
+    // are the ones stated here, whatever the unrolling
+#pragma clang fp contract(off)
+    constexpr bool ADAM = KIND == EGO_OPT_ADAM;
+    __shared__ float s_bc1[ADAM ? EGO_ADAMW_MAX_GROUPS : 1], s_bc2[ADAM ? EGO_ADAMW_MAX_GROUPS : 1];
+    const int gated = gate ? gate[0] : 0;
+    if (gated && !zero_grad) return;
+    if (ADAM) {
+        if (!gated && threadIdx.x < EGO_ADAMW_MAX_GROUPS) {
+            const int k = threadIdx.x;
+            float bc1 = hp.bc1[k], bc2 = hp.bc2_sqrt[k];
+            if (gate && k < hp.n_groups) {         // adamw_seg_kernel's count and corrections
+                int t = hp.step[k] - gate[1];
+                if (t < 1) t = 1;
+                bc1 = (float)(1.0 - pow((double)b1, (double)t));
+                bc2 = (float)sqrt(1.0 - pow((double)b2, (double)t));
+            }
+            s_bc1[k] = bc1;
+            s_bc2[k] = bc2;
+        }
+        __syncthreads();
+    }
+    float coef = gscale;
+    if (max_norm > 0.f && sqnorm) {
+        coef *= fminf(1.f, max_norm / fmaf((float)sqrt(*sqnorm), gscale, 1e-6f));       // adamw_seg_kernel's coef
+    }
+    for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        int a = 0, b = n_segs - 1;                  // the last segment whose first chunk is <= c
+        while (a < b) {
+            const int mid = (a + b + 1) >> 1;
+            if (chunks[mid] <= c) a = mid; else b = mid - 1;
+        }
+        const ego_adamw_seg sg = segs[a];
+        const long lo = sg.lo + (c - chunks[a]) * SEG_CHUNK;
+        const long hi = lo + SEG_CHUNK < sg.hi ? lo + SEG_CHUNK : sg.hi;
+        const int grp = __builtin_amdgcn_readfirstlane(sg.group);
+        // (as in adamw_seg_kernel: a table that does not fit is refused by the entry point from its host copy, and nothing outside
+        //  [0, n) or the block is touched even if the device copy disagrees with it)
+        if (sg.lo < 0 || sg.hi > n || lo < sg.lo || (unsigned)grp >= (unsigned)EGO_ADAMW_MAX_GROUPS) continue;
+        if (gated || (sg.flags & EGO_SEG_FROZEN)) {
+            if (zero_grad)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+                    if (i < hi) *(f32x4*)(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            continue;
+        }
+        const float lr = hp.lr[grp], wd = hp.wd[grp];
+        float step = lr, bc2_sqrt = 1.f;
+        if (ADAM) {
+            step = lr / s_bc1[grp];
+            bc2_sqrt = s_bc2[grp];
+        }
+        f32x4 pp[4], gg[4], mm[4], vv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+            if (i < hi) {
+                pp[k] = *(f32x4*)(p + i); gg[k] = *(f32x4*)(g + i); mm[k] = *(f32x4*)(m + i);
+                if (ADAM) vv[k] = *(f32x4*)(v + i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long i = lo + ((long)k * 256 + threadIdx.x) * 4;
+            if (i >= hi) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = fmaf(wd, pp[k][e], gg[k][e] * coef);
+                if (ADAM) {
+                    mm[k][e] = fmaf(b1, mm[k][e], (1.f - b1) * d);
+                    vv[k][e] = fmaf(b2, vv[k][e], (1.f - b2) * d * d);
+                    pp[k][e] = fmaf(-step, mm[k][e] / (sqrtf(vv[k][e]) / bc2_sqrt + eps), pp[k][e]);
+                } else {
+                    mm[k][e] = fmaf(momentum, mm[k][e], d);
+                    const float u = KIND == EGO_OPT_NESTEROV ? fmaf(momentum, mm[k][e], d) : mm[k][e];
+                    pp[k][e] = fmaf(-lr, u, pp[k][e]);
+                }
+            }
+            *(f32x4*)(p + i) = pp[k]; *(f32x4*)(m + i) = mm[k];
+            if (ADAM) *(f32x4*)(v + i) = vv[k];
+            if (zero_grad) *(f32x4*)(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int ego_optim_step_seg(float* p, float* g, float* m, float* v, long n, const ego_adamw_seg* segs_host,
+                                  const ego_adamw_seg* segs, int n_segs, const long* chunks, const ego_adamw_hp* hp, float beta1,
+                                  float beta2, float eps, float gscale, float max_norm, const double* sqnorm, int zero_grad,
+                                  const int* gate, int kind, float momentum, hipStream_t stream) {
+    if (kind != EGO_OPT_ADAM && kind != EGO_OPT_SGD && kind != EGO_OPT_NESTEROV) return EGO_ERR_ARG;
+    const bool adam = kind == EGO_OPT_ADAM;
+    if (!adam && !(momentum >= 0.f && momentum <= 3.0e38f)) return EGO_ERR_ARG;             // (NaN and inf fail the comparisons)
+    if (n_segs < 0 || n < 0 || !hp || hp->n_groups < 0 || hp->n_groups > EGO_ADAMW_MAX_GROUPS) return EGO_ERR_ARG;
+    if (((uintptr_t)p) % 16 || ((uintptr_t)g) % 16 || ((uintptr_t)m) % 16 || (adam && (!v || ((uintptr_t)v) % 16)) ||
+        ((uintptr_t)gate) % 4 || ((uintptr_t)sqnorm) % 8)
+        return EGO_ERR_ARG;
+    if (n_segs == 0) return EGO_OK;
+    if (!p || !g || !m || !segs_host || !segs || !chunks || ((uintptr_t)segs) % 8 || ((uintptr_t)chunks) % 8) return EGO_ERR_ARG;
+    long n_chunks = 0, prev = 0;
+    for (int s = 0; s < n_segs; ++s) {
+        const ego_adamw_seg& sg = segs_host[s];
+        if (sg.lo < prev || sg.hi <= sg.lo || sg.hi > n || (sg.lo & 3) || (sg.hi & 3)) return EGO_ERR_ARG;
+        if (sg.group < 0 || sg.group >= hp->n_groups) return EGO_ERR_ARG;
+        if (adam && !(sg.flags & EGO_SEG_FROZEN) && hp->step[sg.group] < 1) return EGO_ERR_ARG;
+        prev = sg.hi;
+        n_chunks += (sg.hi - sg.lo + SEG_CHUNK - 1) / SEG_CHUNK;
+    }
+    ego_adamw_hp h = *hp;                           // passed by value, as in ego_adamw_step_seg
+    if (adam && !gate)
+        for (int k = 0; k < h.n_groups; ++k) {      // as ego_adamw_step forms them
+            const int t = h.step[k] < 1 ? 1 : h.step[k];
+            h.bc1[k] = (float)(1.0 - pow((double)beta1, (double)t));
+            h.bc2_sqrt[k] = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+        }
+    const int blocks = (int)(n_chunks < 4096 ? n_chunks : 4096);
+    if (adam) {
+        EGO_LAUNCH(optim_seg_kernel<EGO_OPT_ADAM>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n, segs, n_segs, chunks, n_chunks,
+                   h, beta1, beta2, eps, momentum, gscale, max_norm, sqnorm, zero_grad, gate);
+    } else if (kind == EGO_OPT_SGD) {
+        EGO_LAUNCH(optim_seg_kernel<EGO_OPT_SGD>, dim3(blocks), dim3(256), 0, stream, p, g, m, (float*)nullptr, n, segs, n_segs,
+                   chunks, n_chunks, h, beta1, beta2, eps, momentum, gscale, max_norm, sqnorm, zero_grad, gate);
+    } else {
+        EGO_LAUNCH(optim_seg_kernel<EGO_OPT_NESTEROV>, dim3(blocks), dim3(256), 0, stream, p, g, m, (float*)nullptr, n, segs, n_segs,
+                   chunks, n_chunks, h, beta1, beta2, eps, momentum, gscale, max_norm, sqnorm, zero_grad, gate);
+    }
+    LAUNCH_CHECK();
+    return EGO_OK;
+}
+
 // ---- model EMA: a moving average of the flat parameter buffer, and the in-place exchange that applies it ---------------------
 //
 // Replaces: ModelEmaV2.update (egom2p/utils/timm/model_ema.py:128-132: `ema_v.copy_(decay * ema_v + (1 - decay) * model_v)` per

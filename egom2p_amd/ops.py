@@ -488,6 +488,32 @@ def adamw_step_seg(p, g, m, v, table, hp, beta1=0.9, beta2=0.95, eps=1e-8, gscal
                                       _stream()), "ego_adamw_step_seg")
 
 
+OPT_KINDS = {"adam": L.OPT_ADAM, "momentum": L.OPT_SGD, "nesterov": L.OPT_NESTEROV}
+SGD_KINDS = ("momentum", "nesterov")        # one state buffer (`m` is the momentum buffer), no `v`
+
+
+def optim_step_seg(kind, p, g, m, v, table, hp, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0, gscale=1.0, max_norm=0.0, sqnorm=None,
+                   zero_grad=False, gate=None):
+    """`adamw_step_seg`'s launch for the other optimisers of the reference (optim_factory.py:217-224).  kind: "adam" (torch.optim.Adam:
+    the weight decay goes into the gradient), "momentum" (torch.optim.SGD with momentum) or "nesterov" (the same with nesterov=True);
+    an L.OPT_* value passes through.  The SGD kinds take v=None, `m` is their momentum buffer, and the slots' step counts are not read."""
+    code = OPT_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+    if isinstance(code, str):
+        raise L.EgoHipError(f"optim_step_seg: unknown optimiser kind '{kind}' (one of {sorted(OPT_KINDS)})")
+    _need_cuda(p, g, m, v, table.dev, table.chunks)
+    if gate is not None and (gate.dtype != torch.int32 or gate.numel() < GATE_WORDS):
+        raise L.EgoHipError("optim_step_seg: gate must hold GATE_WORDS int32")
+    if len(hp) > L.ADAMW_MAX_GROUPS:
+        raise L.EgoHipError(f"optim_step_seg: {len(hp)} hyper-parameter slots, the block holds {L.ADAMW_MAX_GROUPS}")
+    blk = L.AdamwHp()
+    blk.n_groups = len(hp)
+    for k, (lr, wd, step) in enumerate(hp):
+        blk.lr[k], blk.wd[k], blk.step[k] = lr, wd, int(step)
+    check(L.load().ego_optim_step_seg(_p(p), _p(g), _p(m), _p(v), p.numel(), table.host, _p(table.dev), len(table), _p(table.chunks),
+                                      C.byref(blk), beta1, beta2, eps, gscale, max_norm, _p(sqnorm), int(zero_grad), _p(gate),
+                                      code, momentum, _stream()), "ego_optim_step_seg")
+
+
 def _flat_f32(name, *ts):
     _need_cuda(*ts)
     for t in ts:

@@ -134,13 +134,15 @@ class FusedAdamW:
     Without it the optimiser has the two groups `decay` / `no_decay` and steps one launch per run of equal weight-decay class;
     with it every group, step offset and frozen range is a segment of ONE `ops.adamw_step_seg` launch."""
 
+    kind = "adamw"                                 # `FusedOptimizer` below: "adam", "momentum", "nesterov"
+
     def __init__(self, engine, lr: float = 1e-4, weight_decay: float = 0.05, betas=(0.9, 0.95), eps: float = 1e-8,
                  named_parameters=None, world_size: int = 1, param_groups=None):
         self.engine = engine
         self.betas, self.eps = betas, eps
         self.world_size = world_size
         self.m = torch.zeros_like(engine.P)
-        self.v = torch.zeros_like(engine.P)
+        self.v = torch.zeros_like(engine.P) if self.kind not in ops.SGD_KINDS else None     # (SGD: `m` is the momentum buffer)
         self.sqnorm = torch.zeros(1, device=engine.dev, dtype=torch.float64)
         self.t = 0
         named = list(named_parameters) if named_parameters is not None else []
@@ -307,10 +309,9 @@ class FusedAdamW:
             for table, slots in launches:
                 hp = [(float(self.param_groups[gi]["lr"]), float(self.param_groups[gi]["weight_decay"]), self.t - sk)
                       for gi, sk in slots] or [(0.0, 0.0, 1)]
-                ops.adamw_step_seg(eng.P, eng.G, self.m, self.v, table, hp, self.betas[0], self.betas[1], self.eps, gscale=gscale,
-                                   max_norm=float(clip_grad) if clip_grad else 0.0,
-                                   sqnorm=self.sqnorm if (clip_grad or gated) else None, zero_grad=zero_grad,
-                                   gate=self.gate if gated else None)
+                self._launch_seg(table, hp, gscale=gscale, max_norm=float(clip_grad) if clip_grad else 0.0,
+                                 sqnorm=self.sqnorm if (clip_grad or gated) else None, zero_grad=zero_grad,
+                                 gate=self.gate if gated else None)
             eng.weights_dirty = True
             self.last_grad_norm = norm
             return norm
@@ -331,6 +332,10 @@ class FusedAdamW:
         self.last_grad_norm = norm
         return norm
 
+    def _launch_seg(self, table, hp, **kw):
+        eng = self.engine
+        ops.adamw_step_seg(eng.P, eng.G, self.m, self.v, table, hp, self.betas[0], self.betas[1], self.eps, **kw)
+
     def zero_grad(self, set_to_none: bool = False):
         self.engine.G.zero_()
 
@@ -343,6 +348,11 @@ class FusedAdamW:
                 "param_groups": [{k: v for k, v in g.items() if k not in ("params", "param_names")} for g in self.param_groups]}
 
     def load_state_dict(self, sd):
+        if sd.get("kind", "adamw") != self.kind:
+            raise RuntimeError(f"optimizer state was saved by the optimiser kind '{sd.get('kind', 'adamw')}', this optimiser is "
+                               f"'{self.kind}' (--opt): their state buffers mean different things; build it with the same --opt, "
+                               "or restart the optimizer state")
+        moments = ("m",) if self.v is None else ("m", "v")
         have, want = sd.get("layout"), self.engine.layout_tag()
         if have is None:
             # (before round 5 the state carried no tag, and round 5 moved the decoder's context_norm weights inside the flat buffers:
@@ -355,9 +365,10 @@ class FusedAdamW:
             # a run with fixed positional tables continued with learned ones: the learned tables lie behind everything the saved
             # state covers, so the saved moments are the head of this engine's; the tables start like any parameter new to AdamW -
             # zero moments, bias correction from step 1 (`skipped`, as for a tensor unfrozen later)
-            self.m.zero_(); self.v.zero_()
-            self.m[:body].copy_(sd["m"]); self.v[:body].copy_(sd["v"])
-            sd = dict(sd, m=self.m, v=self.v, layout=want,
+            for k in moments:
+                getattr(self, k).zero_()
+                getattr(self, k)[:body].copy_(sd[k])
+            sd = dict(sd, layout=want, **{k: getattr(self, k) for k in moments},
                       skipped=dict(sd.get("skipped", {}), **{n: int(sd["t"]) for n in self.engine.offsets if n.endswith("pos_emb")}))
             have = want
         if tuple(have) != tuple(want):
@@ -371,7 +382,9 @@ class FusedAdamW:
             raise RuntimeError(f"optimizer state was saved with the parameter groups {saved[:4]}{'...' if len(saved) > 4 else ''} "
                                f"({len(saved)}), this optimiser has {mine[:4]}{'...' if len(mine) > 4 else ''} ({len(mine)}): build it "
                                "with the same layer_decay / decoder_decay / no_lr_scale_list, or restart the optimizer state")
-        self.m.copy_(sd["m"]); self.v.copy_(sd["v"]); self.t = int(sd["t"])
+        for k in moments:
+            getattr(self, k).copy_(sd[k])
+        self.t = int(sd["t"])
         self.skipped = {str(k): int(v) for k, v in sd.get("skipped", {}).items()}
         # the restored counts are folded ones: whatever this optimiser's device block counted belongs to the state it replaces
         if self.gate is not None:
@@ -383,13 +396,77 @@ class FusedAdamW:
             g.update(s)
 
 
+class FusedOptimizer(FusedAdamW):
+    """The other optimisers of the reference's `--opt` (optim_factory.py:217-224) on the segmented launch, `ops.optim_step_seg`:
+    kind "adam" (torch.optim.Adam: the weight decay is added to the gradient), "momentum" (torch.optim.SGD with momentum) and
+    "nesterov" (the same with nesterov=True).  Everything around the per-element rule is `FusedAdamW`'s: groups with lr /
+    weight_decay / lr_scale, frozen ranges (out of the clip norm, gradients zeroed), the step gate, and for Adam the per-tensor
+    step offsets.  Without `param_groups` the segment table is the two-group (decay / no_decay) one.
+    State: Adam keeps `m` and `v`; the SGD kinds keep `m` alone - the momentum buffer - and allocate no `v` (4 B per parameter
+    less).  A tensor that sat steps out starts from its zero buffer, as torch's SGD starts a parameter without state."""
+
+    def __init__(self, engine, kind: str, lr: float = 1e-4, weight_decay: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 momentum: float = 0.9, named_parameters=None, world_size: int = 1, param_groups=None):
+        if kind not in ops.OPT_KINDS:
+            raise ValueError(f"FusedOptimizer: unknown kind '{kind}' (one of {sorted(ops.OPT_KINDS)}; AdamW is FusedAdamW)")
+        if kind in ops.SGD_KINDS:
+            if not momentum >= 0.0:                 # torch.optim.SGD's own refusals
+                raise ValueError(f"Invalid momentum value: {momentum}")
+            if kind == "nesterov" and momentum <= 0:
+                raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.kind = kind
+        self.momentum = float(momentum)
+        named = list(named_parameters) if named_parameters is not None else []
+        if param_groups is None:                    # FusedAdamW's default grouping, as a segment table
+            if not named:
+                raise ValueError("FusedOptimizer needs named_parameters (tensors are placed by name)")
+            param_groups = [
+                {"name": "decay", "weight_decay": weight_decay, "lr_scale": 1.0,
+                 "params": [p for n, p in named if not is_no_decay(n)], "param_names": [n for n, _ in named if not is_no_decay(n)]},
+                {"name": "no_decay", "weight_decay": 0.0, "lr_scale": 1.0,
+                 "params": [p for n, p in named if is_no_decay(n)], "param_names": [n for n, _ in named if is_no_decay(n)]},
+            ]
+        super().__init__(engine, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, named_parameters=named,
+                         world_size=world_size, param_groups=param_groups)
+
+    def segments(self):
+        if self.kind not in ops.SGD_KINDS:
+            return super().segments()
+        eng = self.engine                           # (no bias correction: a step offset does not split a segment)
+        frozen = {eng._canon_key(n) for n, p in self._named if not p.requires_grad}
+        return build_segments(eng.offsets, eng.never_grad, self._group_of, {}, frozen)
+
+    def _launch_seg(self, table, hp, **kw):
+        eng = self.engine
+        ops.optim_step_seg(self.kind, eng.P, eng.G, self.m, self.v, table, hp, self.betas[0], self.betas[1], self.eps,
+                           momentum=self.momentum, **kw)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["kind"] = self.kind
+        if self.v is None:                          # one buffer: `m`, the momentum buffer
+            del sd["v"]
+            sd["momentum"] = self.momentum
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)                 # (refuses a state of another kind)
+        if self.v is None and "momentum" in sd:
+            self.momentum = float(sd["momentum"])
+
+
 def create_optimizer(args, model, get_num_layer=None, get_layer_scale=None, filter_bias_and_bn=True, skip_list=None):
-    """`create_optimizer` of the reference (optim_factory.py:157-230), AdamW only.  `get_num_layer` (name -> layer id) and
-    `get_layer_scale` (layer id -> lr scale) give layer-wise lr decay; `args.decoder_decay` (a weight decay of its own for names
-    starting `decoder.`) and `args.no_lr_scale_list` ("a-b-c": names that keep scale 1) are read as the reference reads them
-    (:163-170).  With none of them the optimiser is the two-group one on its per-run launches."""
-    if getattr(args, "opt", "adamw").lower().split("_")[-1] != "adamw":
-        raise NotImplementedError("only AdamW is on the accelerated path")
+    """`create_optimizer` of the reference (optim_factory.py:157-230).  `args.opt` picks the optimiser as there (:214-229, the part
+    behind the last "_"): `sgd` / `nesterov` -> SGD with Nesterov momentum, `momentum` -> SGD with plain momentum (both read
+    `args.momentum` and drop eps), `adam` -> Adam, `adamw` -> AdamW; anything else is a ValueError.  `get_num_layer` (name -> layer
+    id) and `get_layer_scale` (layer id -> lr scale) give layer-wise lr decay; `args.decoder_decay` (a weight decay of its own for
+    names starting `decoder.`) and `args.no_lr_scale_list` ("a-b-c": names that keep scale 1) are read as the reference reads them
+    (:163-170).  With none of them AdamW is the two-group optimiser on its per-run launches; the other kinds always step on the
+    segmented launch, over the same two groups."""
+    opt = getattr(args, "opt", "adamw").lower().split("_")[-1]
+    kind = {"sgd": "nesterov", "nesterov": "nesterov", "momentum": "momentum", "adam": "adam", "adamw": "adamw"}.get(opt)
+    if kind is None:
+        raise ValueError(f"Invalid optimizer '{args.opt}': one of sgd, nesterov, momentum, adam, adamw (optim_factory.py:217-229)")
     betas = tuple(args.opt_betas) if getattr(args, "opt_betas", None) else (0.9, 0.999)
     eps = args.opt_eps if getattr(args, "opt_eps", None) else 1e-8
     world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
@@ -410,6 +487,10 @@ def create_optimizer(args, model, get_num_layer=None, get_layer_scale=None, filt
         skip = skip_list if skip_list is not None else (model.no_weight_decay() if hasattr(model, "no_weight_decay") else ())
         dec = model.decoder_weight_decay() if hasattr(model, "decoder_weight_decay") else ()
         groups = get_parameter_groups(model, args.weight_decay, skip, get_num_layer, get_layer_scale, decoder_decay, dec, no_lr_scale)
+    if kind != "adamw":
+        return FusedOptimizer(model.engine, kind, lr=args.lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
+                              momentum=getattr(args, "momentum", 0.9), named_parameters=model.named_parameters(), world_size=world,
+                              param_groups=groups)
     return FusedAdamW(model.engine, lr=args.lr, weight_decay=args.weight_decay, betas=betas, eps=eps,
                       named_parameters=model.named_parameters(), world_size=world, param_groups=groups)
 

@@ -178,6 +178,10 @@ class KernelTimer:
         def c_adamw_seg(p, g, m, v, table, hp, *a, **kw):
             return 0.0, 28.0 * table.elems_active + 4.0 * table.elems_frozen      # p, m, v read and written, g read and zeroed | g zeroed
 
+        def c_optim_seg(kind, p, g, m, v, table, hp, *a, **kw):
+            per = 20.0 if v is None else 28.0                           # c_adamw_seg's count: p, m (and v) read and written, g read
+            return 0.0, per * table.elems_active + 4.0 * table.elems_frozen
+
         def c_ema_update(ema, p, decay):
             return 0.0, float(ema.numel()) * 12.0                       # p and ema read, ema written
 
@@ -196,7 +200,7 @@ class KernelTimer:
         other = {"droppath_draw": c_droppath_draw, "droppath_resid": c_droppath_resid, "droppath_scale": c_droppath_scale,
                  "compact": c_compact, "embed_fwd": c_embed_fwd, "embed_bwd": c_embed_bwd, "loss_perm": c_loss_perm,
                  "loss_finalize": c_loss_finalize, "cast_weight": c_cast_weight, "cast_f32_bf16": c_cast, "bias_grad": c_bias_grad,
-                 "grad_sqnorm": c_sqnorm, "adamw_step": c_adamw, "adamw_step_seg": c_adamw_seg,
+                 "grad_sqnorm": c_sqnorm, "adamw_step": c_adamw, "adamw_step_seg": c_adamw_seg, "optim_step_seg": c_optim_seg,
                  "ema_update": c_ema_update, "swap_f32": c_swap}
         self.cost_table = dict(table, **other)
         saved = {}

@@ -539,7 +539,8 @@ int ego_adamw_step_gated(float* p, float* g, float* m, float* v, long n, float l
                          int step, float gscale, float max_norm, const double* sqnorm, int zero_grad, const int* gate,
                          hipStream_t stream);
 /* The parameter-group AdamW (one launch over a segment table: ego_adamw_step_seg, its structs and limits) is declared in
- * egom2p_hip_optim.h, which this header includes at its end. */
+ * egom2p_hip_optim.h, which this header includes at its end; Adam, SGD with momentum and Nesterov on the same launch
+ * (ego_optim_step_seg) in egom2p_hip_optim_kinds.h behind it. */
 
 /* Model EMA over the flat parameter buffer (ModelEmaV2.update, egom2p/utils/timm/model_ema.py:128-132:
  * `ema_v.copy_(decay * ema_v + (1. - decay) * model_v)` for every state-dict tensor): ema[i] = decay * ema[i] + one_minus_decay * p[i]
@@ -577,4 +578,5 @@ int ego_dp_wait(ego_dp_comm* comm, hipStream_t compute_stream, hipStream_t comm_
 #endif
 
 #include "egom2p_hip_optim.h"       /* extension entries: same library, same ABI version */
+#include "egom2p_hip_optim_kinds.h" /* Adam / SGD / Nesterov on the segmented launch */
 #endif

@@ -73,7 +73,9 @@ def get_args(argv=None):
                         "nn.Parameter (1, n_pos, dim) per modality, N(0, 0.02)) instead of the fixed sin-cos buffers; a checkpoint of a "
                         "sin-cos run loads into such a model, its fixed tables as the starting values")
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "bf16"])
-    p.add_argument("--opt", default="adamw")
+    p.add_argument("--opt", default="adamw", type=str,
+                   help="Optimizer (default: %(default)s): adamw | adam | sgd | nesterov (both: SGD with Nesterov momentum) | momentum (SGD "
+                        "with plain momentum); of a name with underscores the last part counts")
     p.add_argument("--opt_eps", default=1e-8, type=float)
     p.add_argument("--opt_betas", default=[0.9, 0.95], type=float, nargs="+")
     p.add_argument("--clip_grad", default=None, type=float)
@@ -86,6 +88,7 @@ def get_args(argv=None):
     p.add_argument("--model_ema_decay", default=0.9999, type=float, help="ema = decay * ema + (1 - decay) * model")
     p.add_argument("--model_ema_warmup", action="store_true",
                    help="decay of update k is min(decay, (1 + k) / (10 + k)): a short run does not keep its initial weights")
+    p.add_argument("--momentum", type=float, default=0.9, help="SGD momentum (default: %(default)s)")
     p.add_argument("--weight_decay", default=0.05, type=float)
     p.add_argument("--weight_decay_end", default=None, type=float, help="final weight decay (default: constant)")
     p.add_argument("--layer_decay", default=None, type=float,
@@ -353,7 +356,8 @@ def main(args):
         scale_fn = LayerDecayValueAssigner(layer_decay_values(args.layer_decay, depth_e + depth_d)).get_scale
     optimizer = create_optimizer(args, model.module, get_num_layer=layer_fn, get_layer_scale=scale_fn)
     if rank == 0 and optimizer.segmented:
-        print("Param groups: " + ", ".join(f"{g['name']} lr_scale {g['lr_scale']:.4f} wd {g['weight_decay']:g} ({len(g['params'])})"
+        print(f"Param groups (optimizer {optimizer.kind}" + (f", momentum {optimizer.momentum:g}" if optimizer.kind in ("momentum", "nesterov") else "") +
+              "): " + ", ".join(f"{g['name']} lr_scale {g['lr_scale']:.4f} wd {g['weight_decay']:g} ({len(g['params'])})"
                                            for g in optimizer.param_groups), flush=True)
     # (every rank keeps its own average: the ranks' parameters are bitwise equal after every step, so the averages are too)
     model_ema = ModelEma(model.module, decay=args.model_ema_decay, warmup=args.model_ema_warmup) if args.model_ema else None
